@@ -20,7 +20,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def _bench(*args):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--rehearse", "--no-cpu-baseline",
+    # --full: the cross-rank checks and config 4's reduce-scatter are not part of a plain run
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--rehearse", "--full", "--no-cpu-baseline",
                         "--settle-ms", "20", *args], capture_output=True, text=True, timeout=300, env=env, cwd=REPO)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [x for x in p.stdout.splitlines() if x.startswith("{")]

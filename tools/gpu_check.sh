@@ -10,7 +10,7 @@ tail -2 $OUT/gputests.log
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { echo SMOKE_FAILED; tail -20 $OUT/smoke.log; exit 1; }
 tail -1 $OUT/smoke.log
 for wl in orswot "$@"; do
-  timeout -k 10 300 python bench.py --workload $wl > $OUT/bench_$wl.json 2> $OUT/bench_$wl.err || { echo BENCH_FAILED $wl; tail -20 $OUT/bench_$wl.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --workload $wl > $OUT/bench_$wl.json 2> $OUT/bench_$wl.err || { echo BENCH_FAILED $wl; tail -20 $OUT/bench_$wl.err; exit 1; }
   echo "$wl $(cut -c1-400 $OUT/bench_$wl.json)"
 done
 bash tools/profile.sh $TAG || { echo PROF_FAILED; exit 1; }
