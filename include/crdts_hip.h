@@ -519,6 +519,76 @@ int crdt_map_mvreg_merge(crdt_ctx* ctx, const crdt_map_mvreg_slab* self, const c
                          const crdt_map_mvreg_slab* out, size_t n_obj, uint32_t n_actors, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * Map<K, MVReg<u64, A>, A>::apply (CmRDT), batched: out[i] := self[i] after
+ * Map::apply (src/map.rs:160-190) of each of object i's ops, in order, in the
+ * slab's canonical form (keys ascending, MVReg values in Vec order, deferred
+ * clocks in CLOCK ORDER, deferred key sets ascending). Only the used slots of
+ * out are written. Object i's ops are [obj_end[i-1], obj_end[i]) of the op
+ * arrays (all device arrays); op j's clock — an Rm's clock, an Up's Put
+ * clock — is the (actor, counter) pairs [clk_end[j-1], clk_end[j]) of clk_act
+ * / clk_ctr, actors strictly increasing, counters non-zero.
+ *
+ * The reference's rules, as applied:
+ *  - Op::Nop (:165): nothing.
+ *  - Op::Up, duplicate dot (:170-173): if map.clock.get(actor) >= counter the
+ *    WHOLE op is skipped — no Put, no apply_deferred. A dot with counter 0 is
+ *    therefore a no-op.
+ *  - Op::Up otherwise (:175-187): the entry is taken out, or starts from an
+ *    empty clock and an empty MVReg; entry.clock.witness(dot) (a max); the
+ *    Put (MVReg::apply, src/mvreg.rs:158-186): an empty Put clock leaves the
+ *    values untouched (:161-163) — the entry is still inserted, possibly with
+ *    zero values; otherwise every value whose clock is <= the Put clock is
+ *    dropped (:165), then (clock, val) is appended unless a remaining
+ *    value's clock is strictly greater (:173-183); the entry is re-inserted;
+ *    map.clock.witness(dot); apply_deferred.
+ *  - Op::Rm -> apply_rm(key, clock) (:336-350): if !(clock <= map.clock) it
+ *    is deferred — the key joins the set of an equal deferred clock, or a new
+ *    deferred entry is inserted at its CLOCK ORDER position; then, if the
+ *    entry exists, clock is subtracted from its clock and an emptied entry is
+ *    removed, else MVReg::truncate(clock) (src/mvreg.rs:100-113), which may
+ *    leave an entry with zero values. An empty Rm clock changes nothing.
+ *  - apply_deferred (:325-333): all deferred entries are taken and cleared,
+ *    and every (clock, key) goes through apply_rm again. With MVReg values
+ *    each step is a subtract and subtracts commute: the result does not
+ *    depend on the reference's HashMap order. The pass covers every deferred
+ *    key, not only the updated one.
+ *
+ * CRDT_EINVAL (before any device work): a null ctx / self / ops / out;
+ * n_actors == 0 or > 128; self capacities outside crdt_map_mvreg_merge's
+ * per-side limits; an out capacity below self's or above kcap 8192, mcap 256,
+ * dcap 128, scap 8192; a null slab array with n_obj > 0; a null op array its
+ * count says is non-empty (obj_end: n_obj; kind .. clk_end: n_ops; clk_act,
+ * clk_ctr: n_clk); out->clock == self->clock (the call is not in place, and
+ * no out array may overlap a self array). n_obj == 0 is CRDT_OK; an object
+ * without ops is copied through.
+ * Latched per object (the other objects are unaffected, the object's output
+ * row is unspecified): CRDT_ECAPACITY when at any step of its op list —
+ * intermediate states count, as in crdt_orswot_apply — the state needs more
+ * than out's kcap, mcap, dcap or scap; CRDT_ENONCANON for an input row the
+ * merge rejects (a count above its capacity), obj_end / clk_end decreasing or
+ * past n_ops / n_clk (nothing outside the op arrays is read), an unknown
+ * kind, a dot actor >= n_actors, an op clock whose actors are not strictly
+ * increasing or that holds a zero counter or an actor >= n_actors.          */
+#define CRDT_MAP_OP_NOP 0u /* Op::Nop */
+#define CRDT_MAP_OP_RM 1u  /* Op::Rm { clock, key } */
+#define CRDT_MAP_OP_UP 2u  /* Op::Up { dot: (actor, counter), key, op: MVReg Op::Put { clock, val } } */
+typedef struct crdt_map_mvreg_ops {
+  const uint64_t* obj_end;   /* device, n_obj */
+  const uint32_t* kind;      /* device, n_ops */
+  const uint64_t* key;       /* device, n_ops (Rm, Up) */
+  const uint32_t* actor;     /* device, n_ops (Up: the dot) */
+  const uint64_t* counter;   /* device, n_ops (Up: the dot) */
+  const uint64_t* val;       /* device, n_ops (Up: the Put's value) */
+  const uint64_t* clk_end;   /* device, n_ops */
+  const uint32_t* clk_act;   /* device, n_clk */
+  const uint64_t* clk_ctr;   /* device, n_clk */
+  size_t n_ops;
+  size_t n_clk;
+} crdt_map_mvreg_ops;
+int crdt_map_mvreg_apply(crdt_ctx* ctx, const crdt_map_mvreg_slab* self, const crdt_map_mvreg_ops* ops,
+                         const crdt_map_mvreg_slab* out, size_t n_obj, uint32_t n_actors, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * Map<K, Map<K, MVReg<u64, A>, A>, A>::merge, batched: the reference's own
  * Map test type (TestMap, test/map.rs:4-8; Map::merge src/map.rs:191-268 with
  * the inner map's merge and Causal::truncate :131-158 as the value's). Keys

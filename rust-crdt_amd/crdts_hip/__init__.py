@@ -17,7 +17,7 @@ import os
 
 import numpy as np
 
-from ._lib import (CRDT_COMM_ID_BYTES, CRDT_ECAPACITY, CRDT_ENONCANON, CRDT_OK, EXPORTS, LIB_PATH, SPARSE_CLOCK, Batch, CrdtError,
+from ._lib import (CRDT_COMM_ID_BYTES, CRDT_ECAPACITY, CRDT_EINVAL, CRDT_ENONCANON, CRDT_OK, EXPORTS, LIB_PATH, SPARSE_CLOCK, Batch, CrdtError,
                    GenParams, RepParams, check, lib)
 from .record import decode_record, encode_record, record_bytes
 
@@ -25,7 +25,7 @@ __all__ = [
     "Engine", "OrswotBatch", "GenParams", "CrdtError", "generate_orswot", "generate_dense", "HostOrswot",
     "Orswot", "VClock", "GCounter", "PNCounter", "merge_batch", "decode_record", "encode_record",
     "record_bytes", "CONFIG3", "EXPORTS", "LIB_PATH", "CONFIG5", "SPARSE_CLOCK", "generate_replicas", "ClockBatch",
-    "generate_clocks_csr", "MapMapSlab",
+    "generate_clocks_csr", "MapMapSlab", "MapOps",
 ]
 
 # SURVEY.md §8(d) config 3 / BASELINE.json configs[2].
@@ -210,6 +210,70 @@ class OrswotOps:
             return torch.from_numpy(np.asarray(x, dtype=np.uint32).view(np.int32)).to(dev)
 
         return cls(u64(ends), u32(kind), u64(mem), u32(act), u64(ctr), u64(cend), u32(cact), u64(cctr))
+
+
+class MapOps:
+    """A batch of Map<u64, MVReg<u64, A>, A> ops (Op::Nop / Op::Rm / Op::Up
+    with an MVReg Put, src/map.rs:104-125) on the device, grouped per object in
+    order (crdt_map_mvreg_ops)."""
+
+    NOP, RM, UP = 0, 1, 2
+
+    def __init__(self, obj_end, kind, key, actor, counter, val, clk_end, clk_act, clk_ctr):
+        self.t = (obj_end, kind, key, actor, counter, val, clk_end, clk_act, clk_ctr)
+        self.n_obj = int(obj_end.numel())
+        self.n_ops = int(kind.numel())
+        self.n_clk = int(clk_act.numel())
+
+    def cops(self):
+        from ._lib import MapOpsC
+
+        p = [C.c_void_p(t.data_ptr()) if t.numel() else None for t in self.t]
+        return MapOpsC(*p, self.n_ops, self.n_clk)
+
+    @classmethod
+    def from_arrays(cls, obj_end, kind, key, actor, counter, val, clk_end, clk_act, clk_ctr, device=0):
+        """Host numpy arrays (u64 / u32 as in crdt_map_mvreg_ops) -> device."""
+        torch = _torch()
+        dev = f"cuda:{device}"
+
+        def put(x, u32):
+            x = np.ascontiguousarray(np.asarray(x, dtype=np.uint32 if u32 else np.uint64))
+            return torch.from_numpy(x.view(np.int32 if u32 else np.int64)).to(dev)
+
+        return cls(put(obj_end, False), put(kind, True), put(key, False), put(actor, True), put(counter, False),
+                   put(val, False), put(clk_end, False), put(clk_act, True), put(clk_ctr, False))
+
+    @staticmethod
+    def arrays_from_lists(per_obj):
+        """per_obj[i] = [("up", actor, counter, key, [(a, c), ...], val) | ("rm", key, [(a, c), ...]) | ("nop",), ...]
+        -> the nine host arrays of crdt_map_mvreg_ops."""
+        ends, kind, key, act, ctr, val, cend, cact, cctr = [], [], [], [], [], [], [], [], []
+        for ops in per_obj:
+            for op in ops:
+                if op[0] == "up":
+                    kind.append(MapOps.UP); act.append(op[1]); ctr.append(op[2]); key.append(op[3]); val.append(op[5])
+                    pairs = op[4]
+                elif op[0] == "rm":
+                    kind.append(MapOps.RM); act.append(0); ctr.append(0); key.append(op[1]); val.append(0)
+                    pairs = op[2]
+                elif op[0] == "nop":
+                    kind.append(MapOps.NOP); act.append(0); ctr.append(0); key.append(0); val.append(0)
+                    pairs = ()
+                else:
+                    raise ValueError(f"unknown map op {op[0]!r}")
+                for a, c in pairs:
+                    cact.append(a); cctr.append(c)
+                cend.append(len(cact))
+            ends.append(len(kind))
+        return (np.asarray(ends, np.uint64), np.asarray(kind, np.uint32), np.asarray(key, np.uint64),
+                np.asarray(act, np.uint32), np.asarray(ctr, np.uint64), np.asarray(val, np.uint64),
+                np.asarray(cend, np.uint64), np.asarray(cact, np.uint32), np.asarray(cctr, np.uint64))
+
+    @classmethod
+    def from_lists(cls, per_obj, device=0):
+        """per_obj[i] = [("up", actor, counter, key, [(a, c), ...], val) | ("rm", key, [(a, c), ...]) | ("nop",), ...]"""
+        return cls.from_arrays(*cls.arrays_from_lists(per_obj), device=device)
 
 
 class MapSlab:
@@ -777,6 +841,28 @@ class Engine:
         if check_status:
             self.status(stream)
         return R
+
+    def map_mvreg_apply(self, S: "MapSlab", ops: "MapOps", n_actors, out_caps=None, out=None, stream=None,
+                        check_status=True):
+        """out[i] = S[i] after Map::apply (src/map.rs:160-190) of object i's ops
+        in order; returns the output slab (`out`, or a new one of capacities
+        out_caps = (kcap, mcap, dcap, scap), default: S's plus one key, value
+        and deferred clock per op of the longest op list, within the call's
+        limits). Only the used slots of the output are written. Not in place."""
+        n = int(S.a["n_keys"].shape[0])
+        if out is None:
+            if out_caps is None:
+                ends = ops.t[0].cpu().numpy().view(np.uint64) if ops.n_obj else np.zeros(0, np.uint64)
+                grow = int(np.diff(ends, prepend=np.uint64(0)).max()) if ends.size else 0
+                out_caps = (min(8192, S.kcap + grow), min(256, S.mcap + grow), min(128, S.dcap + grow),
+                            min(8192, S.scap + grow))
+            out = MapSlab.alloc(n, n_actors, *out_caps, device=S.a["clock"].device)
+        s, o, r = S.cstruct(), ops.cops(), out.cstruct()
+        check(lib.crdt_map_mvreg_apply(self.ctx, C.byref(s), C.byref(o), C.byref(r), n, n_actors,
+                                       self._stream(stream)), "map_mvreg_apply")
+        if check_status:
+            self.status(stream)
+        return out
 
     # ------------------------------------------------ Map<u64, Map<u64, MVReg<u64>>>
     def map_map_merge(self, S: "MapMapSlab", O: "MapMapSlab", n_actors, stream=None, check_status=True, out=None):

@@ -77,7 +77,7 @@ EXPORTS = [
     "crdt_dense_merge_host", "crdt_vclock_csr_merge", "crdt_gcounter_csr_merge", "crdt_pncounter_csr_merge",
     "crdt_orswot_truncate", "crdt_ctx_host_syncs", "crdt_orswot_fold", "crdt_ctx_set_arena_limit",
     "crdt_map_map_merge_scratch_bytes", "crdt_map_map_merge", "crdt_replica_allreduce_max_transport",
-    "crdt_replica_reduce_scatter_max_transport",
+    "crdt_replica_reduce_scatter_max_transport", "crdt_map_mvreg_apply",
 ]
 
 CRDT_COMM_ID_BYTES = 128
@@ -103,6 +103,12 @@ class Ops(C.Structure):
     _fields_ = [("obj_end", C.c_void_p), ("kind", C.c_void_p), ("member", C.c_void_p), ("actor", C.c_void_p),
                 ("counter", C.c_void_p), ("clk_end", C.c_void_p), ("clk_act", C.c_void_p),
                 ("clk_ctr", C.c_void_p), ("n_ops", C.c_size_t), ("n_clk", C.c_size_t)]
+
+
+class MapOpsC(C.Structure):
+    """crdt_map_mvreg_ops (include/crdts_hip.h)."""
+    _fields_ = [(f, C.c_void_p) for f in ("obj_end", "kind", "key", "actor", "counter", "val", "clk_end", "clk_act",
+                                          "clk_ctr")] + [("n_ops", C.c_size_t), ("n_clk", C.c_size_t)]
 
 
 class MapSlabC(C.Structure):
@@ -222,6 +228,7 @@ def _load():
         "crdt_vclock_partial_cmp": (I, [P, P, P, SZ, U32, P, P]),
         "crdt_mvreg_merge": (I, [P, P, P, P, U32, P, P, P, U32, P, P, P, U32, SZ, U32, P]),
         "crdt_map_mvreg_merge": (I, [P, C.POINTER(MapSlabC), C.POINTER(MapSlabC), C.POINTER(MapSlabC), SZ, U32, P]),
+        "crdt_map_mvreg_apply": (I, [P, C.POINTER(MapSlabC), C.POINTER(MapOpsC), C.POINTER(MapSlabC), SZ, U32, P]),
         "crdt_map_orswot_merge": (I, [P, C.POINTER(MapOrswotSlabC), C.POINTER(MapOrswotSlabC),
                                       C.POINTER(MapOrswotSlabC), SZ, U32, P]),
         "crdt_map_map_merge_scratch_bytes": (SZ, [C.POINTER(MapMapSlabC), SZ, U32]),

@@ -600,6 +600,26 @@ static bool map_mvreg_ptrs_ok(const crdt_map_mvreg_slab* x) {
          x->dset_n && x->dset;
 }
 
+int crdt_map_mvreg_apply(crdt_ctx* ctx, const crdt_map_mvreg_slab* self, const crdt_map_mvreg_ops* ops,
+                         const crdt_map_mvreg_slab* out, size_t n_obj, uint32_t n_actors, void* stream) {
+  if (!ctx || !self || !ops || !out || n_actors == 0 || n_actors > 128) return CRDT_EINVAL;
+  if (!map_mvreg_caps_ok(self)) return CRDT_EINVAL;
+  // the largest output of a merge (the sums of its per-side limits)
+  if (out->kcap < self->kcap || out->kcap > 8192 || out->mcap < self->mcap || out->mcap > 256 ||
+      out->dcap < self->dcap || out->dcap > 128 || out->scap < self->scap || out->scap > 8192)
+    return CRDT_EINVAL;
+  if (n_obj) {
+    if (!map_mvreg_ptrs_ok(self) || !map_mvreg_ptrs_ok(out) || !ops->obj_end) return CRDT_EINVAL;
+    if (out->clock == self->clock) return CRDT_EINVAL;  // not in place
+  }
+  if (ops->n_ops && (!ops->kind || !ops->key || !ops->actor || !ops->counter || !ops->val || !ops->clk_end))
+    return CRDT_EINVAL;
+  if (ops->n_clk && (!ops->clk_act || !ops->clk_ctr)) return CRDT_EINVAL;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_map_mvreg_apply(*self, *ops, *out, n_obj, n_actors, ctx->d_status, ctx->d_ctl, S(stream));
+}
+
 size_t crdt_map_map_merge_scratch_bytes(const crdt_map_map_slab* out, size_t n_obj, uint32_t n_actors) {
   return out ? map_map_scratch_bytes(*out, n_obj, n_actors) : 0u;
 }

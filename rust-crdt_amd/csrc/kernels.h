@@ -78,6 +78,10 @@ int launch_mvreg_merge(const uint32_t* sn, const uint64_t* sclk, const uint64_t*
 
 int launch_map_mvreg_merge(const crdt_map_mvreg_slab& S, const crdt_map_mvreg_slab& O, const crdt_map_mvreg_slab& R,
                            uint64_t n_obj, uint32_t A, int* status, uint32_t* ctl, hipStream_t stream, int variant = 0);
+// Map<u64, MVReg>::apply (map_apply.hip): R row i = S row i after its ops of P
+// in order; R's capacities >= S's (api.hip)
+int launch_map_mvreg_apply(const crdt_map_mvreg_slab& S, const crdt_map_mvreg_ops& P, const crdt_map_mvreg_slab& R,
+                           uint64_t n_obj, uint32_t A, int* status, uint32_t* ctl, hipStream_t stream);
 // The nested map's inner pass (map_map.hip): task t merges S row tsrc[2t]
 // with O row tsrc[2t + 1] (~0: an absent side) into R row t, truncated by Tb
 // row t when it is non-empty (one pass: no intermediate slab).

@@ -1,0 +1,362 @@
+"""GPU parity: Map<u64, MVReg<u64, A>, A>::apply, batched (crdt_map_mvreg_apply,
+rust-crdt_amd/csrc/map_apply.hip) — slab-row exact against the C++ oracle's
+op path and the Python restatement (Map::apply src/map.rs:160-190, apply_rm
+:336-350, apply_deferred :325-333, MVReg Put src/mvreg.rs:158-186), the
+reference's two op-path Map KATs with every apply on the kernel, and the
+call's error contract (include/crdts_hip.h)."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+
+import map_kat_runner as mkr
+import map_opgen
+import map_slab
+from map_slab import crdts_ref
+
+pytestmark = pytest.mark.gpu
+A = 8
+IN_CAPS, OUT_CAPS = (4, 4, 4, 4), (8, 8, 8, 8)
+
+
+def _patterned(n, n_actors, caps):
+    """A device output slab holding a pattern: the kernel writes only the used
+    slots, so canonical forms are compared."""
+    import crdts_hip
+
+    out = crdts_hip.MapSlab.alloc(n, n_actors, *caps, device="cuda")
+    for v in out.a.values():
+        v.fill_(0x5A5A5A5A)
+    return out
+
+
+def _apply(gpu, S, per_obj, n_actors, caps, **kw):
+    import crdts_hip
+
+    n = S.a["n_keys"].shape[0]
+    ops = per_obj if isinstance(per_obj, crdts_hip.MapOps) else crdts_hip.MapOps.from_lists(per_obj)
+    return gpu.map_mvreg_apply(S.to("cuda"), ops, n_actors, out=_patterned(n, n_actors, caps), **kw)
+
+
+def _assert_rows(got, exp, rows=None, what=""):
+    g, e = got.canonical(), exp.canonical()
+    n = e.a["n_keys"].shape[0]
+    rows = np.arange(n) if rows is None else np.asarray(rows)
+    for f in e.a:
+        d = (np.asarray(g.a[f]) != np.asarray(e.a[f])).reshape(n, -1).any(axis=1)[rows]
+        bad = rows[np.nonzero(d)[0]]
+        assert bad.size == 0, f"{what} {f}: {bad.size} objects differ, first {bad[:5].tolist()}"
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(seed, n, n_actors):
+    """(batch, S, E): the generated streams, the input rows and the oracle's
+    rows after the whole stream — computed once, never modified."""
+    import oracle_ffi
+
+    batch = map_opgen.gen_batch(seed, n, n_actors)
+    S, E = map_opgen.oracle_slabs(oracle_ffi, batch, n_actors, IN_CAPS, OUT_CAPS)
+    return batch, S, E
+
+
+# ------------------------------------------------------------------ 1. KATs
+class GpuApplyBackend(mkr.PyMapBackend):
+    """Every apply_up_put / apply_rm is one crdt_map_mvreg_apply call: the map
+    and the op are interned to dense actor ids over state ∪ op
+    (order-preserving), the map is written to a one-row slab, the op applied
+    by the kernel, and the row read back. After every apply the state must be
+    the Python restatement's."""
+
+    def __init__(self, eng):
+        self.eng = eng
+        self.applies = 0
+
+    def _apply(self, m, op):
+        clock = op[4] if op[0] == "up" else op[2]
+        acts = sorted(map_slab.actors_of(m) | {a for a, _ in clock} | ({op[1]} if op[0] == "up" else set())) or [0]
+        fwd = {a: i for i, a in enumerate(acts)}
+        back = {i: a for a, i in fwd.items()}
+        n = len(acts)
+        rel = [(fwd[a], c) for a, c in clock]
+        gop = ("up", fwd[op[1]], op[2], op[3], rel, op[5]) if op[0] == "up" else ("rm", op[1], rel)
+        import crdts_hip
+
+        S = crdts_hip.MapSlab.alloc(1, n, *IN_CAPS)
+        map_slab.mvreg_map_to_row(map_slab.relabel(m, fwd), S, 0, n)
+        R = _apply(self.eng, S, [[gop]], n, OUT_CAPS).host()
+        out = map_slab.relabel(map_slab.mvreg_map_from_row(R, 0), back)
+        exp = m.clone()
+        map_opgen.apply_op(exp, op)
+        assert out == exp, (op, out.canonical(), exp.canonical())
+        m.clock, m.entries, m.deferred = out.clock, out.entries, out.deferred
+        self.applies += 1
+
+    def apply_up_put(self, m, dot, key, put_pairs, val):
+        self._apply(m, ("up", dot[0], dot[1], key, [tuple(p) for p in put_pairs], val))
+
+    def apply_rm(self, m, key, pairs):
+        self._apply(m, ("rm", key, [tuple(p) for p in pairs]))
+
+
+KATS = [c for c in mkr.load_cases() if c["name"] in ("test_op_exchange_commutes_quickcheck1",
+                                                      "test_op_deferred_remove")]
+
+
+@pytest.mark.parametrize("case", KATS, ids=[c["name"] for c in KATS])
+def test_map_op_kat_on_gpu(case, gpu):
+    assert len(KATS) == 2
+    be = GpuApplyBackend(gpu)
+    got = mkr.run_case(case, be)  # the reference's asserts, on kernel-made states
+    assert be.applies == sum(st[0] == "apply" for st in case["steps"])
+    exp = mkr.run_case(case, mkr.PyMapBackend())
+    assert all(got[k] == exp[k] for k in exp)
+
+
+# ------------------------------------------------------- 2. random parity
+def test_map_apply_random_parity(gpu, oracle):
+    """2,000 generated objects, the whole stream in one call: exact against the
+    C++ oracle."""
+    batch, S, E = _reference(0xA991, 2000, A)
+    assert (S.a["n_keys"] > 0).sum() > 400 and (E.a["n_def"] > 0).sum() > 200
+    _assert_rows(_apply(gpu, S, [ops for _, ops in batch], A, OUT_CAPS), E)
+
+
+def test_map_apply_chained_single_ops(gpu, oracle):
+    """The first 200 of them, one op per call, each call's output the next
+    call's input: every intermediate state exact against the C++ oracle."""
+    import crdts_hip
+
+    batch, S, _ = _reference(0xA991, 2000, A)
+    batch = batch[:200]
+    n = len(batch)
+    hs = []
+    for pre, _ in batch:
+        h = oracle.OracleMap("mvreg")
+        for op in pre:
+            map_opgen.apply_op_oracle(h, op)
+        hs.append(h)
+    cur = crdts_hip.MapSlab({f: v[:n].copy() for f, v in S.a.items()}, *IN_CAPS).to("cuda")
+    L = oracle.lib()
+    for t in range(max(len(ops) for _, ops in batch)):
+        step = [ops[t:t + 1] for _, ops in batch]
+        exp = crdts_hip.MapSlab.alloc(n, A, *OUT_CAPS)
+        e = exp.cstruct()
+        for i, (h, ops) in enumerate(zip(hs, step)):
+            for op in ops:
+                map_opgen.apply_op_oracle(h, op)
+            assert L.orc_mapmv_to_slab(h.h, C.byref(e), i, A) == 0
+        cur = gpu.map_mvreg_apply(cur, crdts_hip.MapOps.from_lists(step), A, out=_patterned(n, A, OUT_CAPS))
+        _assert_rows(cur, exp, what=f"step {t}")
+
+
+def test_map_apply_long_op_lists(gpu, oracle):
+    """Op lists past 64 ops and 64 clock pairs per object: the kernel stages
+    op headers 64 at a time with the first 64 clock pairs of each chunk, and
+    reads the pairs past that window from the op arrays."""
+    rng = map_opgen.random.Random(0x10E6)
+    batch = [map_opgen.gen_object(rng, A, n_ops=n, fold=bool(i & 1), val0=1000 * i)
+             for i, n in enumerate([100, 150, 200, 12, 260, 90, 64, 65])]
+    assert max(len(ops) for _, ops in batch) > 128
+    assert sum(len(op[4] if op[0] == "up" else op[2]) for op in batch[2][1][:64]) > 64
+    caps = (8, 8, 32, 8)
+    S, E = map_opgen.oracle_slabs(oracle, batch, A, caps, caps)
+    _assert_rows(_apply(gpu, S, [ops for _, ops in batch], A, caps), E)
+
+
+# ------------------------------------------------- 3. actor-width boundaries
+@pytest.mark.parametrize("n_actors", [64, 65, 100, 128])
+def test_map_apply_actor_widths(gpu, oracle, n_actors):
+    """One slot per lane up to 64 actors, two from 65: the last lane of each
+    slot (actors 63, 64, n_actors - 1) carries dots and clock entries."""
+    batch, S, E = _reference(0xB0 + n_actors, 300, n_actors)
+    assert E.a["clock"][:, n_actors - 1].any() and E.a["clock"][:, 63].any()
+    assert n_actors == 64 or E.a["clock"][:, 64:].any()
+    _assert_rows(_apply(gpu, S, [ops for _, ops in batch], n_actors, OUT_CAPS), E)
+
+
+# -------------------------------- 4. ordered structures past one wave's lanes
+def _wide_case():
+    """A map of 70 keys and 62 deferred clocks, and an op list that edits the
+    front, the middle and the end of its keys, of its deferred clocks (CLOCK
+    ORDER) and of a deferred key set."""
+    m = crdts_ref.Map(crdts_ref.MVReg)
+    for k in range(70):  # keys 10, 20, .. 700; map clock {0: 70}
+        m.apply_up((0, k + 1), 10 * (k + 1), lambda r, k=k: r.apply_put(crdts_ref.VClock([(0, k + 1)]), k))
+    for d in range(62):  # deferred [(2, 100)] .. [(2, 161)], each naming the absent key 5
+        m.apply_rm(5, crdts_ref.VClock([(2, 100 + d)]))
+    assert len(m.entries) == 70 and len(m.deferred) == 62
+    ops = [
+        ("up", 1, 1, 1, [(0, 70), (1, 1)], 1000),        # a key below the first
+        ("up", 1, 2, 355, [(0, 70), (1, 2)], 1001),      # between two keys
+        ("up", 1, 3, 10000, [(0, 70), (1, 3)], 1002),    # above the last
+        ("rm", 1, [(1, 1)]),                             # the first entry emptied
+        ("rm", 350, [(0, 35)]),                          # a middle entry
+        ("rm", 10000, [(1, 3)]),                         # the last entry
+        ("rm", 20, [(0, 71)]),                           # future clocks: the front of CLOCK ORDER (drops key 20),
+        ("rm", 30, [(2, 130), (3, 1)]),                  # the middle ([(2, 130)] is its proper prefix),
+        ("rm", 20, [(3, 5), (4, 1)]),                    # the end,
+        ("rm", 30, [(3, 5)]),                            # and a proper prefix of the last one, before it
+        ("rm", 2, [(2, 110)]),                           # an existing deferred clock: a key below its set's {5}
+        ("rm", 999, [(2, 110)]),                         # and one above
+        ("rm", 40, [(1, 4)]),                            # a deferred clock in the middle ([(0,71)] < it < [(2,100)])
+        ("up", 1, 4, 40, [(0, 70), (1, 4)], 1003),       # the Up that retires it, and only it
+        ("nop",),
+    ]
+    return m, ops
+
+
+def test_map_apply_wide_ordered_structures(gpu):
+    import crdts_hip
+
+    m, ops = _wide_case()
+    in_caps, out_caps = (80, 2, 64, 4), (80, 2, 80, 4)
+    S = crdts_hip.MapSlab.alloc(1, A, *in_caps)
+    map_slab.mvreg_map_to_row(m, S, 0, A)
+    # the whole list in one call
+    exp = m.clone()
+    for op in ops:
+        map_opgen.apply_op(exp, op)
+    assert len(exp.deferred) == 62 + 4 and len(exp.entries) == 69  # ([(0, 71)] also empties key 20's entry)
+    assert sorted(exp.deferred[crdts_ref.VClock([(2, 110)])]) == [2, 5, 999]
+    E = crdts_hip.MapSlab.alloc(1, A, *out_caps)
+    map_slab.mvreg_map_to_row(exp, E, 0, A)
+    _assert_rows(_apply(gpu, S, [ops], A, out_caps), E, what="one call")
+    # and every prefix of the list (a map past 64 deferred clocks is no input
+    # of the call: the states are not chained)
+    py = m.clone()
+    for t, op in enumerate(ops):
+        before = len(py.deferred)
+        map_opgen.apply_op(py, op)
+        if t == 13:
+            assert before == 67 and len(py.deferred) == 66  # the Up retired one deferred clock
+        map_slab.mvreg_map_to_row(py, E, 0, A)
+        _assert_rows(_apply(gpu, S, [ops[:t + 1]], A, out_caps), E, what=f"op {t} {op}")
+
+
+# ------------------------------------------------ 5. copy-through and empties
+def test_map_apply_copy_through_and_empties(gpu, oracle):
+    import crdts_hip
+
+    gen = map_opgen.gen_batch(0xE0, 8, A)
+    full = lambda i: gen[i][0] + gen[i][1]  # noqa: E731
+    batch = [(full(0), gen[1][1]),            # a map with ops
+             (full(2), []),                   # no ops, between two that have some
+             (full(3), gen[4][1]),
+             ([], [("nop",)] + full(5)),      # an all-empty self map
+             ([], [])]                        # empty map, no ops
+    S, E = map_opgen.oracle_slabs(oracle, batch, A, IN_CAPS, OUT_CAPS)
+    assert S.a["n_keys"][1] > 0 and S.a["n_keys"][3] == 0 and not S.a["clock"][3].any()
+    _assert_rows(_apply(gpu, S, [ops for _, ops in batch], A, OUT_CAPS), E)
+    # n_ops == 0: null op arrays, every object copied through
+    none = crdts_hip.MapOps.from_lists([[] for _ in batch])
+    assert none.n_ops == 0 and none.cops().kind is None and none.cops().clk_act is None
+    W = crdts_hip.MapSlab({f: v.copy() for f, v in S.a.items()}, *IN_CAPS)
+    _assert_rows(_apply(gpu, S, none, A, IN_CAPS), W)
+    # n_obj == 0
+    Z = crdts_hip.MapSlab.alloc(0, A, *IN_CAPS)
+    out = gpu.map_mvreg_apply(Z.to("cuda"), crdts_hip.MapOps.from_lists([]), A, out_caps=OUT_CAPS)
+    assert out.a["n_keys"].shape[0] == 0
+
+
+# ------------------------------------------------------------------ 6. errors
+def _overflowing(which):
+    """An op list that needs 5 slots of `which` (out capacity 4)."""
+    if which == "kcap":
+        return [("up", 0, k + 1, 100 + k, [(0, k + 1)], k) for k in range(5)]
+    if which == "mcap":  # five concurrent values of one key
+        return [("up", a, 1, 7, [(a, 1)], a) for a in range(5)]
+    if which == "dcap":  # five future clocks
+        return [("rm", 7, [(3, 10 + d)]) for d in range(5)]
+    return [("rm", 100 + k, [(3, 10)]) for k in range(5)]  # scap: five keys under one future clock
+
+
+@pytest.mark.parametrize("which", ["kcap", "mcap", "dcap", "scap"])
+def test_map_apply_capacity(gpu, oracle, which):
+    import crdts_hip
+
+    gen = map_opgen.gen_batch(0xA991, 2, A)
+    caps = tuple(4 if c == which else 8 for c in ("kcap", "mcap", "dcap", "scap"))
+    batch = [gen[0], ([], _overflowing(which)), gen[1]]
+    S, E = map_opgen.oracle_slabs(oracle, [gen[0], ([], _overflowing(which)[:4]), gen[1]], A, IN_CAPS, caps)
+    # four of the five fit: the status is clean and the row exact
+    _assert_rows(_apply(gpu, S, [gen[0][1], _overflowing(which)[:4], gen[1][1]], A, caps), E)
+    with pytest.raises(crdts_hip.CrdtError) as e:
+        _apply(gpu, S, [ops for _, ops in batch], A, caps)
+    assert e.value.code == crdts_hip.CRDT_ECAPACITY
+    got = _apply(gpu, S, [ops for _, ops in batch], A, caps, check_status=False)
+    with pytest.raises(crdts_hip.CrdtError):
+        gpu.status()
+    _assert_rows(got, E, rows=[0, 2], what="neighbours")
+    gpu.status()  # the latch is cleared: the context is usable again
+
+
+def _raw_ops(per_obj, **patch):
+    import crdts_hip
+
+    names = ("obj_end", "kind", "key", "actor", "counter", "val", "clk_end", "clk_act", "clk_ctr")
+    arrs = dict(zip(names, crdts_hip.MapOps.arrays_from_lists(per_obj)))
+    for k, v in patch.items():
+        arrs[k] = np.asarray(v, dtype=arrs[k].dtype)
+    return crdts_hip.MapOps.from_arrays(*(arrs[k] for k in names))
+
+
+GOOD = [("up", 0, 1, 7, [(0, 1)], 5)]
+NONCANON = {
+    "descending_clock_actors": lambda: _raw_ops([GOOD, [("rm", 3, [(2, 1), (1, 1)])], GOOD]),
+    "equal_clock_actors": lambda: _raw_ops([GOOD, [("rm", 3, [(2, 1), (2, 2)])], GOOD]),
+    "zero_counter": lambda: _raw_ops([GOOD, [("rm", 3, [(1, 0)])], GOOD]),
+    "clock_actor_out_of_range": lambda: _raw_ops([GOOD, [("rm", 3, [(A, 1)])], GOOD]),
+    "dot_actor_out_of_range": lambda: _raw_ops([GOOD, [("up", A, 1, 3, [(0, 1)], 5)], GOOD]),
+    "kind_3": lambda: _raw_ops([GOOD, [("nop",)], GOOD], kind=[2, 3, 2]),
+    "decreasing_obj_end": lambda: _raw_ops([GOOD, GOOD, GOOD], obj_end=[2, 1, 3]),
+    "obj_end_past_n_ops": lambda: _raw_ops([GOOD, GOOD, GOOD], obj_end=[1, 9, 3]),
+    "clk_end_past_n_clk": lambda: _raw_ops([GOOD, GOOD, GOOD], clk_end=[1, 7, 3]),
+}
+
+
+@pytest.mark.parametrize("name", sorted(NONCANON))
+def test_map_apply_noncanonical_ops(gpu, name):
+    """A malformed op list latches CRDT_ENONCANON for its object; the first
+    object of the batch, whose list is well formed, is exact."""
+    import crdts_hip
+
+    S = crdts_hip.MapSlab.alloc(3, A, *IN_CAPS)
+    exp = crdts_ref.Map(crdts_ref.MVReg)
+    map_opgen.apply_op(exp, GOOD[0])
+    E = crdts_hip.MapSlab.alloc(3, A, *OUT_CAPS)
+    map_slab.mvreg_map_to_row(exp, E, 0, A)
+    got = _apply(gpu, S, NONCANON[name](), A, OUT_CAPS, check_status=False)
+    with pytest.raises(crdts_hip.CrdtError) as e:
+        gpu.status()
+    assert e.value.code == crdts_hip.CRDT_ENONCANON
+    _assert_rows(got, E, rows=[0], what=name)
+    gpu.status()
+
+
+def test_map_apply_noncanonical_input_row(gpu):
+    """An input row the merge rejects: a value count above mcap."""
+    import crdts_hip
+
+    S = crdts_hip.MapSlab.alloc(1, A, *IN_CAPS)
+    m = crdts_ref.Map(crdts_ref.MVReg)
+    map_opgen.apply_op(m, GOOD[0])
+    map_slab.mvreg_map_to_row(m, S, 0, A)
+    S.a["mv_n"][0, 0] = IN_CAPS[1] + 1
+    with pytest.raises(crdts_hip.CrdtError) as e:
+        _apply(gpu, S, [[]], A, OUT_CAPS)
+    assert e.value.code == crdts_hip.CRDT_ENONCANON
+
+
+def test_map_apply_einval(gpu):
+    import crdts_hip
+
+    S = crdts_hip.MapSlab.alloc(1, A, *IN_CAPS).to("cuda")
+    ops = crdts_hip.MapOps.from_lists([GOOD])
+    for kw in (dict(n_actors=129, out_caps=OUT_CAPS), dict(n_actors=A, out_caps=(3, 8, 8, 8)),
+               dict(n_actors=A, out_caps=(8, 8, 8, 3)), dict(n_actors=A, out_caps=(8200, 8, 8, 8)),
+               dict(n_actors=A, out=S)):
+        with pytest.raises(crdts_hip.CrdtError) as e:
+            gpu.map_mvreg_apply(S, ops, **kw)
+        assert e.value.code == crdts_hip.CRDT_EINVAL, kw
+    gpu.status()
