@@ -680,6 +680,95 @@ int crdt_map_orswot_merge(crdt_ctx* ctx, const crdt_map_orswot_slab* self, const
                           const crdt_map_orswot_slab* out, size_t n_obj, uint32_t n_actors, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * Map<K, Orswot<u64, A>, A>::apply (CmRDT), batched: out[i] := self[i] after
+ * Map::apply (src/map.rs:160-190) of each of object i's ops, in order, in the
+ * slab's canonical form (keys ascending, members ascending, nested and map
+ * deferred clocks in CLOCK ORDER, their sets ascending). Only the used slots
+ * of out are written. The op batch is laid out as crdt_map_mvreg_ops: object
+ * i's ops are [obj_end[i-1], obj_end[i]) of the op arrays (all device
+ * arrays); op j's clock — a map Rm's clock, or the clock of an Up's nested
+ * Orswot Rm — is the (actor, counter) pairs [clk_end[j-1], clk_end[j]) of
+ * clk_act / clk_ctr, actors strictly increasing, counters non-zero (an
+ * Up{Add}'s pairs are checked the same way and not used). The nested Add's
+ * dot is the Up's dot, as Map::update builds it (src/map.rs:306-317 with
+ * Orswot::add, src/orswot.rs:185-187): an Up whose nested Add carries another
+ * dot cannot be expressed.
+ *
+ * The reference's rules, as applied:
+ *  - Op::Nop (:165): nothing.
+ *  - Op::Up, duplicate dot (:170-173): if map.clock.get(actor) >= counter the
+ *    WHOLE op is skipped — no nested op, no apply_deferred.
+ *  - Op::Up otherwise (:175-187): the entry is taken out, or starts from an
+ *    empty clock and an empty Orswot; entry.clock.witness(dot); the nested op;
+ *    the entry is re-inserted, even with an empty set; map.clock.witness(dot);
+ *    apply_deferred.
+ *  - nested Add (src/orswot.rs:66-79): skipped when the set's clock already
+ *    has the dot (the entry clock and the map clock still witness it and the
+ *    map's apply_deferred still runs); else the member's clock takes the dot
+ *    (a max; an absent member is inserted in ascending position), the set's
+ *    clock takes the dot, and the set's apply_deferred (:235-243) runs: every
+ *    step of it is a subtract, so its order does not matter.
+ *  - nested Rm -> apply_remove (src/orswot.rs:195-211): if !(clock <= the
+ *    set's clock) it is deferred in the set — the member joins an equal
+ *    deferred clock's set, or a new deferred entry is inserted at its CLOCK
+ *    ORDER position; then clock is subtracted from the member's clock and an
+ *    emptied member is dropped. An empty clock changes nothing, but the Up
+ *    still happens.
+ *  - Op::Rm -> apply_rm(key, clock) (src/map.rs:336-350): if !(clock <=
+ *    map.clock) it is deferred in the map, as above with keys; then, if the
+ *    entry exists, clock is subtracted from its clock and an emptied entry is
+ *    removed, else Orswot::truncate(clock).
+ *  - Orswot::truncate(clock) (src/orswot.rs:159-172), as in
+ *    crdt_map_orswot_merge: members whose clock is <= clock are dropped; the
+ *    set's clock is joined with clock; the set's apply_deferred runs under
+ *    that clock, retiring the deferred clocks it now covers after removing
+ *    their members; clock is subtracted from the set's clock and from every
+ *    member clock.
+ *  - apply_deferred (src/map.rs:325-333): all deferred entries are taken and
+ *    cleared, and every (clock, key) goes through apply_rm again, in CLOCK
+ *    ORDER and keys ascending — the order crdt_map_orswot_merge uses, and one
+ *    of the orders the reference's HashMap can take. With Orswot values the
+ *    order can change the result.
+ *
+ * CRDT_EINVAL (before any device work): a null ctx / self / ops / out;
+ * n_actors == 0 or > 128; self capacities outside crdt_map_orswot_merge's
+ * per-side limits; an out capacity below self's or above kcap 8192, mcap,
+ * vdcap, vscap, dcap 512, scap 8192; the kernel's per-wave workspace — one
+ * nested set of out's capacities: 8 * (mcap * (1 + n_actors) + vdcap *
+ * (n_actors + vscap)) + 4 * (mcap + 2 * vdcap) bytes — above 60672 bytes
+ * (64 KB less the kernel's op stage and key mirror); a null slab array with n_obj > 0; a null op
+ * array its count says is non-empty (obj_end: n_obj; kind .. clk_end: n_ops;
+ * clk_act, clk_ctr: n_clk); out->clock == self->clock (the call is not in
+ * place, and no out array may overlap a self array). n_obj == 0 is CRDT_OK;
+ * an object without ops is copied through.
+ * Latched per object (the other objects are unaffected, the object's output
+ * row is unspecified): CRDT_ECAPACITY when at any step of its op list —
+ * intermediate states count: a fresh entry, member or deferred clock the
+ * same op then removes still needs its slot — the state needs more than one
+ * of out's six capacities; CRDT_ENONCANON for an input row the merge rejects
+ * (a count above its capacity), obj_end / clk_end decreasing or past n_ops /
+ * n_clk (nothing outside the op arrays is read), an unknown kind, a dot actor
+ * >= n_actors, an op clock whose actors are not strictly increasing or that
+ * holds a zero counter or an actor >= n_actors.                             */
+#define CRDT_MAP_OP_UP_RM 3u /* Op::Up { dot, key, op: Orswot Op::Rm { clock, member } } */
+/* for this call CRDT_MAP_OP_UP (2) is Op::Up { dot, key, op: Orswot Op::Add { dot, member } } */
+typedef struct crdt_map_orswot_ops {
+  const uint64_t* obj_end;   /* device, n_obj */
+  const uint32_t* kind;      /* device, n_ops: NOP 0, RM 1, UP(Add) 2, UP_RM 3 */
+  const uint64_t* key;       /* device, n_ops (Rm, Up) */
+  const uint32_t* actor;     /* device, n_ops (Up: the dot) */
+  const uint64_t* counter;   /* device, n_ops (Up: the dot) */
+  const uint64_t* member;    /* device, n_ops (Up: the nested op's member) */
+  const uint64_t* clk_end;   /* device, n_ops */
+  const uint32_t* clk_act;   /* device, n_clk: a map Rm's clock, or an Up's nested Rm clock */
+  const uint64_t* clk_ctr;   /* device, n_clk */
+  size_t n_ops;
+  size_t n_clk;
+} crdt_map_orswot_ops;
+int crdt_map_orswot_apply(crdt_ctx* ctx, const crdt_map_orswot_slab* self, const crdt_map_orswot_ops* ops,
+                          const crdt_map_orswot_slab* out, size_t n_obj, uint32_t n_actors, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * VClock partial order and MVReg merge, batched.
  * crdt_vclock_partial_cmp: d_out[i] = partial_cmp(a[i], b[i])
  * (src/vclock.rs:59-71) over dense rows u64[n][n_actors], 0 = absent:

@@ -276,6 +276,72 @@ class MapOps:
         return cls.from_arrays(*cls.arrays_from_lists(per_obj), device=device)
 
 
+class MapOrswotOps:
+    """A batch of Map<u64, Orswot<u64, A>, A> ops (Op::Nop / Op::Rm / Op::Up
+    with an Orswot Add or Rm, src/map.rs:104-125) on the device, grouped per
+    object in order (crdt_map_orswot_ops). The nested Add's dot is the Up's."""
+
+    NOP, RM, UP, UP_RM = 0, 1, 2, 3
+
+    def __init__(self, obj_end, kind, key, actor, counter, member, clk_end, clk_act, clk_ctr):
+        self.t = (obj_end, kind, key, actor, counter, member, clk_end, clk_act, clk_ctr)
+        self.n_obj = int(obj_end.numel())
+        self.n_ops = int(kind.numel())
+        self.n_clk = int(clk_act.numel())
+
+    def cops(self):
+        from ._lib import MapOrswotOpsC
+
+        p = [C.c_void_p(t.data_ptr()) if t.numel() else None for t in self.t]
+        return MapOrswotOpsC(*p, self.n_ops, self.n_clk)
+
+    @classmethod
+    def from_arrays(cls, obj_end, kind, key, actor, counter, member, clk_end, clk_act, clk_ctr, device=0):
+        """Host numpy arrays (u64 / u32 as in crdt_map_orswot_ops) -> device."""
+        torch = _torch()
+        dev = f"cuda:{device}"
+
+        def put(x, u32):
+            x = np.ascontiguousarray(np.asarray(x, dtype=np.uint32 if u32 else np.uint64))
+            return torch.from_numpy(x.view(np.int32 if u32 else np.int64)).to(dev)
+
+        return cls(put(obj_end, False), put(kind, True), put(key, False), put(actor, True), put(counter, False),
+                   put(member, False), put(clk_end, False), put(clk_act, True), put(clk_ctr, False))
+
+    @staticmethod
+    def arrays_from_lists(per_obj):
+        """per_obj[i] = [("up_add", actor, counter, key, member) | ("up_rm", actor, counter, key, member,
+        [(a, c), ...]) | ("rm", key, [(a, c), ...]) | ("nop",), ...] -> the nine host arrays of
+        crdt_map_orswot_ops."""
+        ends, kind, key, act, ctr, mem, cend, cact, cctr = [], [], [], [], [], [], [], [], []
+        for ops in per_obj:
+            for op in ops:
+                if op[0] in ("up_add", "up_rm"):
+                    kind.append(MapOrswotOps.UP if op[0] == "up_add" else MapOrswotOps.UP_RM)
+                    act.append(op[1]); ctr.append(op[2]); key.append(op[3]); mem.append(op[4])
+                    pairs = op[5] if op[0] == "up_rm" else ()
+                elif op[0] == "rm":
+                    kind.append(MapOrswotOps.RM); act.append(0); ctr.append(0); key.append(op[1]); mem.append(0)
+                    pairs = op[2]
+                elif op[0] == "nop":
+                    kind.append(MapOrswotOps.NOP); act.append(0); ctr.append(0); key.append(0); mem.append(0)
+                    pairs = ()
+                else:
+                    raise ValueError(f"unknown map op {op[0]!r}")
+                for a, c in pairs:
+                    cact.append(a); cctr.append(c)
+                cend.append(len(cact))
+            ends.append(len(kind))
+        return (np.asarray(ends, np.uint64), np.asarray(kind, np.uint32), np.asarray(key, np.uint64),
+                np.asarray(act, np.uint32), np.asarray(ctr, np.uint64), np.asarray(mem, np.uint64),
+                np.asarray(cend, np.uint64), np.asarray(cact, np.uint32), np.asarray(cctr, np.uint64))
+
+    @classmethod
+    def from_lists(cls, per_obj, device=0):
+        """per_obj[i] = the object's op tuples, as for arrays_from_lists."""
+        return cls.from_arrays(*cls.arrays_from_lists(per_obj), device=device)
+
+
 class MapSlab:
     """Dense fixed-capacity slab of Map<u64, MVReg<u64, A>, A> states
     (crdt_map_mvreg_slab, include/crdts_hip.h). Arrays are numpy (host) or
@@ -904,6 +970,29 @@ class Engine:
         if check_status:
             self.status(stream)
         return R
+
+    MAP_ORSWOT_APPLY_CAP_MAX = {"kcap": 8192, "mcap": 512, "vdcap": 512, "vscap": 512, "dcap": 512, "scap": 8192}
+
+    def map_orswot_apply(self, S: "MapOrswotSlab", ops: "MapOrswotOps", n_actors, out_caps=None, out=None,
+                         stream=None, check_status=True):
+        """out[i] = S[i] after Map::apply (src/map.rs:160-190) of object i's ops
+        in order; returns the output slab (`out`, or a new one of capacities
+        out_caps = dict(kcap, mcap, vdcap, vscap, dcap, scap), default: S's plus
+        one slot per op of the longest op list, within the call's limits). Only
+        the used slots of the output are written. Not in place."""
+        n = S.n
+        if out is None:
+            if out_caps is None:
+                ends = ops.t[0].cpu().numpy().view(np.uint64) if ops.n_obj else np.zeros(0, np.uint64)
+                grow = int(np.diff(ends, prepend=np.uint64(0)).max()) if ends.size else 0
+                out_caps = {k: min(self.MAP_ORSWOT_APPLY_CAP_MAX[k], S.caps[k] + grow) for k in S.caps}
+            out = MapOrswotSlab.alloc(n, n_actors, device=S.a["clock"].device, **out_caps)
+        s, o, r = S.cstruct(), ops.cops(), out.cstruct()
+        check(lib.crdt_map_orswot_apply(self.ctx, C.byref(s), C.byref(o), C.byref(r), n, n_actors,
+                                        self._stream(stream)), "map_orswot_apply")
+        if check_status:
+            self.status(stream)
+        return out
 
     # ------------------------------------------------ batched op path
     def orswot_apply(self, B: "OrswotBatch", ops: "OrswotOps", stream=None, check_status=True):

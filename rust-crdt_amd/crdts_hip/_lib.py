@@ -77,7 +77,7 @@ EXPORTS = [
     "crdt_dense_merge_host", "crdt_vclock_csr_merge", "crdt_gcounter_csr_merge", "crdt_pncounter_csr_merge",
     "crdt_orswot_truncate", "crdt_ctx_host_syncs", "crdt_orswot_fold", "crdt_ctx_set_arena_limit",
     "crdt_map_map_merge_scratch_bytes", "crdt_map_map_merge", "crdt_replica_allreduce_max_transport",
-    "crdt_replica_reduce_scatter_max_transport", "crdt_map_mvreg_apply",
+    "crdt_replica_reduce_scatter_max_transport", "crdt_map_mvreg_apply", "crdt_map_orswot_apply",
 ]
 
 CRDT_COMM_ID_BYTES = 128
@@ -109,6 +109,12 @@ class MapOpsC(C.Structure):
     """crdt_map_mvreg_ops (include/crdts_hip.h)."""
     _fields_ = [(f, C.c_void_p) for f in ("obj_end", "kind", "key", "actor", "counter", "val", "clk_end", "clk_act",
                                           "clk_ctr")] + [("n_ops", C.c_size_t), ("n_clk", C.c_size_t)]
+
+
+class MapOrswotOpsC(C.Structure):
+    """crdt_map_orswot_ops (include/crdts_hip.h)."""
+    _fields_ = [(f, C.c_void_p) for f in ("obj_end", "kind", "key", "actor", "counter", "member", "clk_end",
+                                          "clk_act", "clk_ctr")] + [("n_ops", C.c_size_t), ("n_clk", C.c_size_t)]
 
 
 class MapSlabC(C.Structure):
@@ -230,6 +236,8 @@ def _load():
         "crdt_map_mvreg_merge": (I, [P, C.POINTER(MapSlabC), C.POINTER(MapSlabC), C.POINTER(MapSlabC), SZ, U32, P]),
         "crdt_map_mvreg_apply": (I, [P, C.POINTER(MapSlabC), C.POINTER(MapOpsC), C.POINTER(MapSlabC), SZ, U32, P]),
         "crdt_map_orswot_merge": (I, [P, C.POINTER(MapOrswotSlabC), C.POINTER(MapOrswotSlabC),
+                                      C.POINTER(MapOrswotSlabC), SZ, U32, P]),
+        "crdt_map_orswot_apply": (I, [P, C.POINTER(MapOrswotSlabC), C.POINTER(MapOrswotOpsC),
                                       C.POINTER(MapOrswotSlabC), SZ, U32, P]),
         "crdt_map_map_merge_scratch_bytes": (SZ, [C.POINTER(MapMapSlabC), SZ, U32]),
         "crdt_map_map_merge": (I, [P, C.POINTER(MapMapSlabC), C.POINTER(MapMapSlabC), C.POINTER(MapMapSlabC), SZ,

@@ -673,4 +673,35 @@ int crdt_map_orswot_merge(crdt_ctx* ctx, const crdt_map_orswot_slab* self, const
                                  ctx->variant);
 }
 
+static bool map_orswot_ptrs_ok(const crdt_map_orswot_slab* x) {
+  return x->clock && x->n_keys && x->keys && x->eclock && x->vclock && x->vn_mem && x->vmem && x->vmclock &&
+         x->vn_def && x->vdclock && x->vdset_n && x->vdset && x->n_def && x->dclock && x->dset_n && x->dset;
+}
+
+int crdt_map_orswot_apply(crdt_ctx* ctx, const crdt_map_orswot_slab* self, const crdt_map_orswot_ops* ops,
+                          const crdt_map_orswot_slab* out, size_t n_obj, uint32_t n_actors, void* stream) {
+  if (!ctx || !self || !ops || !out || n_actors == 0 || n_actors > 128) return CRDT_EINVAL;
+  // crdt_map_orswot_merge's per-side limits
+  if (self->kcap == 0 || self->kcap > 4096 || self->mcap == 0 || self->mcap > 256 || self->vdcap == 0 ||
+      self->vdcap > 256 || self->vscap == 0 || self->vscap > 256 || self->dcap == 0 || self->dcap > 256 ||
+      self->scap == 0 || self->scap > 4096)
+    return CRDT_EINVAL;
+  // at most twice them (the largest output of a merge)
+  if (out->kcap < self->kcap || out->kcap > 8192 || out->mcap < self->mcap || out->mcap > 512 ||
+      out->vdcap < self->vdcap || out->vdcap > 512 || out->vscap < self->vscap || out->vscap > 512 ||
+      out->dcap < self->dcap || out->dcap > 512 || out->scap < self->scap || out->scap > 8192)
+    return CRDT_EINVAL;
+  if (map_orswot_apply_lds_bytes(*out, n_actors) > kMapOrswotApplyLdsMax) return CRDT_EINVAL;  // the kernel's workspace
+  if (n_obj) {
+    if (!map_orswot_ptrs_ok(self) || !map_orswot_ptrs_ok(out) || !ops->obj_end) return CRDT_EINVAL;
+    if (out->clock == self->clock) return CRDT_EINVAL;  // not in place
+  }
+  if (ops->n_ops && (!ops->kind || !ops->key || !ops->actor || !ops->counter || !ops->member || !ops->clk_end))
+    return CRDT_EINVAL;
+  if (ops->n_clk && (!ops->clk_act || !ops->clk_ctr)) return CRDT_EINVAL;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_map_orswot_apply(*self, *ops, *out, n_obj, n_actors, ctx->d_status, ctx->d_ctl, S(stream));
+}
+
 }  // extern "C"

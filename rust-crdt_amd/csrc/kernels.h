@@ -97,5 +97,12 @@ int launch_map_orswot_merge(const crdt_map_orswot_slab& S, const crdt_map_orswot
                             const crdt_map_orswot_slab& R, uint64_t n_obj, uint32_t A, int* status, uint32_t* ctl,
                             hipStream_t stream, int variant = 0);
 size_t map_orswot_lds_bytes(const crdt_map_orswot_slab& S, const crdt_map_orswot_slab& O, uint32_t A);
+// Map<u64, Orswot>::apply (map_orswot_apply.hip): R row i = S row i after its
+// ops of P in order; R's capacities >= S's and its workspace within the limit (api.hip)
+int launch_map_orswot_apply(const crdt_map_orswot_slab& S, const crdt_map_orswot_ops& P,
+                            const crdt_map_orswot_slab& R, uint64_t n_obj, uint32_t A, int* status, uint32_t* ctl,
+                            hipStream_t stream);
+size_t map_orswot_apply_lds_bytes(const crdt_map_orswot_slab& R, uint32_t A);
+constexpr size_t kMapOrswotApplyLdsMax = 65536 - 4864;  // 64 KB less the kernel's static op stage and key mirror
 
 }  // namespace crdts_hip

@@ -28,26 +28,18 @@
 
 #include "../../include/crdts_hip.h"
 #include "kernels.h"
+#include "map_orswot_ws.h"
 #include "map_rows.h"
 #include "sched.h"
 
 namespace crdts_hip {
 namespace {
 
-constexpr uint32_t kMoW = 64;
+using namespace mows;  // the LDS nested-set workspace, its apply_deferred and truncate (map_orswot_ws.h)
+
 constexpr uint32_t kMoLdsMax = 65536;  // workspace limit per wave
 constexpr uint32_t kMoStageMax = 16384;  // map deferred staging area limit per wave
 
-__device__ __forceinline__ void mo_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ uint64_t uni64(uint64_t v) {
-  return ((uint64_t)uni((uint32_t)(v >> 32)) << 32) | (uint64_t)uni((uint32_t)v);
-}
-using namespace maprow;  // Row<NS> and the VClock ops on it (map_rows.h)
 __device__ __forceinline__ bool set_has(const uint64_t* set, uint32_t n, uint64_t key, uint32_t lane) {
   bool f = false;
   for (uint32_t j = lane; j < n; j += kMoW) f = f || set[j] == key;
@@ -68,20 +60,6 @@ __device__ __forceinline__ void fill64(uint64_t* dst, uint64_t n, uint32_t lane,
     for (uint64_t e = lane; e < n; e += kMoW) dst[e] = at(e);
   }
 }
-
-// A nested Orswot under construction (LDS). The top clock is a register
-// (lane = actor) held by the caller.
-struct Ws {
-  uint64_t* key;   // [MW] members, ascending
-  uint64_t* row;   // [MW][A] member clocks
-  uint64_t* dclk;  // [DW][A] deferred clocks, CLOCK ORDER
-  uint32_t* dn;    // [DW] set sizes
-  uint64_t* dset;  // [DW][sw] member sets, ascending
-  uint32_t nm, nd, sw;
-};
-struct Caps {
-  uint32_t MW, DW, SW, A;
-};
 
 // Load key slot ki of a slab's nested set into W.
 // Key slot ki of a slab's nested set into W: its two counts (ws_counts, from
@@ -105,71 +83,6 @@ __device__ void ws_copy(Ws& W, const crdt_map_orswot_slab& X, uint64_t ki, const
     const uint32_t d = e / vs;
     W.dset[d * W.sw + (e - d * vs)] = X.vdset[ki * X.vdcap * vs + e];
   }
-}
-
-// Orswot::apply_deferred (src/orswot.rs:235-243) on W under top clock `clk`,
-// after the members flagged in mdead are dropped: every deferred clock is
-// subtracted from the members of its set (a member left empty is dropped),
-// and kept only if `clk` does not cover it. Then both lists are compacted.
-template <int NS>
-__device__ void ws_apply_deferred(Ws& W, Row<NS> clk, uint32_t* mdead, uint32_t* ddead, const Caps& c,
-                                  uint32_t lane) {
-  for (uint32_t d = 0; d < W.nd; ++d) {
-    const Row<NS> D = ldrow<NS>(W.dclk + d * c.A, c.A, lane);
-    const uint32_t n = uni(W.dn[d]);
-    for (uint32_t j = 0; j < n; ++j) {
-      const uint64_t m = uni64(W.dset[d * W.sw + j]);
-      uint32_t lo = 0, hi = W.nm;  // binary search over the (sorted) members
-      while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (uni64(W.key[mid]) < m) lo = mid + 1u;
-        else hi = mid;
-      }
-      if (lo >= W.nm || uni64(W.key[lo]) != m || uni(mdead[lo])) continue;
-      const Row<NS> r = vsub(ldrow<NS>(W.row + lo * c.A, c.A, lane), D);
-      strow(W.row + lo * c.A, r, c.A, lane);
-      const bool gone = !vany(r);
-      mo_sync();
-      if (gone && lane == 0u) mdead[lo] = 1u;
-      mo_sync();
-    }
-    const bool drop = vle(D, clk);
-    if (lane == 0u) ddead[d] = drop ? 1u : 0u;
-  }
-  mo_sync();
-  // compaction, in place (destination <= source)
-  uint32_t k = 0;
-  for (uint32_t j = 0; j < W.nm; ++j) {
-    if (uni(mdead[j])) continue;
-    if (k != j) {
-      const uint64_t key = W.key[j];
-      const Row<NS> r = ldrow<NS>(W.row + j * c.A, c.A, lane);
-      mo_sync();
-      if (lane == 0u) W.key[k] = key;
-      strow(W.row + k * c.A, r, c.A, lane);
-      mo_sync();
-    }
-    ++k;
-  }
-  W.nm = k;
-  k = 0;
-  for (uint32_t d = 0; d < W.nd; ++d) {
-    if (uni(ddead[d])) continue;
-    if (k != d) {
-      const Row<NS> D = ldrow<NS>(W.dclk + d * c.A, c.A, lane);
-      const uint32_t n = uni(W.dn[d]);
-      mo_sync();
-      strow(W.dclk + k * c.A, D, c.A, lane);
-      if (lane == 0u) W.dn[k] = n;
-      for (uint32_t j = lane; j < n; j += kMoW) W.dset[k * W.sw + j] = W.dset[d * W.sw + j];  // (rows k < d)
-      mo_sync();
-    }
-    ++k;
-  }
-  W.nd = k;
-  for (uint32_t j = lane; j < c.MW; j += kMoW) mdead[j] = 0u;
-  for (uint32_t j = lane; j < c.DW; j += kMoW) ddead[j] = 0u;
-  mo_sync();
 }
 
 // Orswot::merge (src/orswot.rs:87-157): Wn = Wc.merge(&Wo), Wo's top clock
@@ -242,25 +155,6 @@ __device__ void ws_merge(const Ws& Wc, const Ws& Wo, Ws& Wn, Row<NS>& sclk, Row<
   sclk = vmax(sclk, oclk);  // :153
   mo_sync();
   ws_apply_deferred(Wn, sclk, mdead, ddead, c, lane);  // :155
-}
-
-// Orswot::truncate (src/orswot.rs:159-172) of W (top clock `clk`) by `t`.
-template <int NS>
-__device__ void ws_truncate(Ws& W, Row<NS>& clk, Row<NS> t, uint32_t* mdead, uint32_t* ddead, const Caps& c,
-                            uint32_t lane) {
-  // merge with an empty set whose clock is t: members t covers are dropped
-  // (:94-104); it has no entries or deferred removes; the clocks merge
-  for (uint32_t j = 0; j < W.nm; ++j) {
-    const bool covered = vle(ldrow<NS>(W.row + j * c.A, c.A, lane), t);
-    if (covered && lane == 0u) mdead[j] = 1u;
-  }
-  clk = vmax(clk, t);
-  mo_sync();
-  ws_apply_deferred(W, clk, mdead, ddead, c, lane);
-  // forget t from the top clock and every member clock (an emptied member stays)
-  clk = vsub(clk, t);
-  for (uint32_t j = 0; j < W.nm; ++j) strow(W.row + j * c.A, vsub(ldrow<NS>(W.row + j * c.A, c.A, lane), t), c.A, lane);
-  mo_sync();
 }
 
 // Write W (top clock clk) into key slot kr of R; false if a capacity is exceeded.

@@ -1,0 +1,479 @@
+"""GPU parity: Map<u64, Orswot<u64, A>, A>::apply, batched
+(crdt_map_orswot_apply, rust-crdt_amd/csrc/map_orswot_apply.hip) — slab-row
+exact against the C++ oracle's op path and the Python restatement (Map::apply
+src/map.rs:160-190, apply_rm :336-350, apply_deferred :325-333 in CLOCK ORDER,
+Orswot::apply src/orswot.rs:66-82, apply_remove :195-211, truncate :159-172),
+the reference's op-path KAT of this type with every apply on the kernel, and
+the call's error contract (include/crdts_hip.h)."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+
+import map_kat_runner as mkr
+import map_orswot_opgen as og
+import map_slab
+from map_slab import crdts_ref
+
+pytestmark = pytest.mark.gpu
+A = 8
+IN_CAPS, OUT_CAPS = og.caps(4), og.caps(8)
+
+
+def _patterned(n, n_actors, caps):
+    """A device output slab holding a pattern: the kernel writes only the used
+    slots, so canonical forms are compared."""
+    import crdts_hip
+
+    out = crdts_hip.MapOrswotSlab.alloc(n, n_actors, device="cuda", **caps)
+    for v in out.a.values():
+        v.fill_(0x5A5A5A5A)
+    return out
+
+
+def _apply(gpu, S, per_obj, n_actors, caps, **kw):
+    import crdts_hip
+
+    ops = per_obj if isinstance(per_obj, crdts_hip.MapOrswotOps) else crdts_hip.MapOrswotOps.from_lists(per_obj)
+    return gpu.map_orswot_apply(S.to("cuda"), ops, n_actors, out=_patterned(S.n, n_actors, caps), **kw)
+
+
+def _assert_rows(got, exp, rows=None, what=""):
+    g, e = got.canonical(), exp.canonical()
+    n = e.n
+    rows = np.arange(n) if rows is None else np.asarray(rows)
+    for f in e.a:
+        d = (np.asarray(g.a[f]) != np.asarray(e.a[f])).reshape(n, -1).any(axis=1)[rows]
+        bad = rows[np.nonzero(d)[0]]
+        assert bad.size == 0, f"{what} {f}: {bad.size} objects differ, first {bad[:5].tolist()}"
+
+
+def _row_slab(m, n_actors, caps):
+    import crdts_hip
+
+    S = crdts_hip.MapOrswotSlab.alloc(1, n_actors, **caps)
+    map_slab.orswot_map_to_row(m, S, 0, n_actors)
+    return S
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(seed, n, n_actors):
+    """(batch, S, E): the generated streams, the input rows and the oracle's
+    rows after the whole stream — computed once, never modified."""
+    import oracle_ffi
+
+    batch = og.gen_batch(seed, n, n_actors)
+    S, E = og.oracle_slabs(oracle_ffi, batch, n_actors, IN_CAPS, OUT_CAPS)
+    return batch, S, E
+
+
+# ------------------------------------------------------------------ 1. the KAT
+class GpuApplyBackend(mkr.PyMapBackend):
+    """Every apply_up_add / apply_rm is one crdt_map_orswot_apply call: the map
+    and the op are interned to dense actor ids over state ∪ op
+    (order-preserving), the map is written to a one-row slab, the op applied
+    by the kernel, and the row read back. After every apply the state must be
+    the Python restatement's."""
+
+    def __init__(self, eng):
+        self.eng = eng
+        self.applies = 0
+
+    def _apply(self, m, op):
+        acts = sorted(map_slab.actors_of(m) | {a for a, _ in og.op_clock(op)} |
+                      ({op[1]} if op[0] != "rm" else set())) or [0]
+        fwd = {a: i for i, a in enumerate(acts)}
+        back = {i: a for a, i in fwd.items()}
+        n = len(acts)
+        if op[0] == "rm":
+            gop = ("rm", op[1], [(fwd[a], c) for a, c in op[2]])
+        else:
+            gop = ("up_add", fwd[op[1]]) + op[2:]
+        R = _apply(self.eng, _row_slab(map_slab.relabel(m, fwd), n, IN_CAPS), [[gop]], n, OUT_CAPS).host()
+        out = map_slab.relabel(map_slab.orswot_map_from_row(R, 0), back)
+        exp = m.clone()
+        og.apply_op(exp, op)
+        assert out == exp, (op, out.canonical(), exp.canonical())
+        m.clock, m.entries, m.deferred = out.clock, out.entries, out.deferred
+        self.applies += 1
+
+    def apply_up_add(self, m, dot, key, member):
+        self._apply(m, ("up_add", dot[0], dot[1], key, member))
+
+    def apply_rm(self, m, key, pairs):
+        self._apply(m, ("rm", key, [tuple(p) for p in pairs]))
+
+
+def test_map_orswot_op_kat_on_gpu(gpu):
+    (case,) = [c for c in mkr.load_cases() if c["name"] == "test_reset_remove_semantics"]
+    assert all(st[2] == "orswot" for st in case["steps"] if st[0] == "new")
+    be = GpuApplyBackend(gpu)
+    got = mkr.run_case(case, be)  # the reference's asserts, on kernel-made states
+    assert be.applies == sum(st[0] == "apply" for st in case["steps"]) > 0
+    exp = mkr.run_case(case, mkr.PyMapBackend())
+    assert all(got[k] == exp[k] for k in exp)
+
+
+# ------------------------------------------------------- 2. random parity
+def test_map_orswot_apply_random_parity(gpu, oracle):
+    """2,000 generated objects, the whole stream in one call: exact against the
+    C++ oracle."""
+    batch, S, E = _reference(0x0A57, 2000, A)
+    assert (S.a["n_keys"] > 0).sum() > 400 and (E.a["n_def"] > 0).sum() > 200
+    assert (E.a["vn_def"] > 0).any(axis=1).sum() > 50 and (E.a["vn_mem"] > 1).any(axis=1).sum() > 200
+    _assert_rows(_apply(gpu, S, [ops for _, ops in batch], A, OUT_CAPS), E)
+
+
+# ------------------------------------------------------- 3. chained
+def test_map_orswot_apply_chained_single_ops(gpu, oracle):
+    """The first 200 of them, one op per call, each call's output the next
+    call's input: every intermediate state exact against the C++ oracle."""
+    import crdts_hip
+
+    batch, S, _ = _reference(0x0A57, 2000, A)
+    batch = batch[:200]
+    n = len(batch)
+    hs = []
+    for pre, _ in batch:
+        h = oracle.OracleMap("orswot")
+        for op in pre:
+            og.apply_op_oracle(h, op)
+        hs.append(h)
+    cur = crdts_hip.MapOrswotSlab({f: v[:n].copy() for f, v in S.a.items()}, IN_CAPS).to("cuda")
+    L = oracle.lib()
+    for t in range(max(len(ops) for _, ops in batch)):
+        step = [ops[t:t + 1] for _, ops in batch]
+        exp = crdts_hip.MapOrswotSlab.alloc(n, A, **OUT_CAPS)
+        e = exp.cstruct()
+        for i, (h, ops) in enumerate(zip(hs, step)):
+            for op in ops:
+                og.apply_op_oracle(h, op)
+            assert L.orc_mapor_to_slab(h.h, C.byref(e), i, A) == 0
+        cur = gpu.map_orswot_apply(cur, crdts_hip.MapOrswotOps.from_lists(step), A, out=_patterned(n, A, OUT_CAPS))
+        _assert_rows(cur, exp, what=f"step {t}")
+
+
+# ------------------------------------------------------- 4. long op lists
+LONG = (64, 65, 100, 150, 12, 200)
+
+
+def test_map_orswot_apply_long_op_lists(gpu, oracle):
+    """Op lists of exactly 64, 65 and 100 ops and past 128, and more than 64
+    clock pairs inside one 64-op chunk: the kernel stages op headers 64 at a
+    time with the first 64 clock pairs of each chunk, and reads the pairs past
+    that window from the op arrays."""
+    rng = og.random.Random(0x10E7)
+    batch = []
+    for i, n in enumerate(LONG):
+        pre, ops = og.gen_object(rng, A, n_ops=2 * n, fold=bool(i & 1))
+        assert len(ops) >= n
+        batch.append((pre, ops[:n]))
+    assert [len(ops) for _, ops in batch] == list(LONG)
+    assert any(sum(len(og.op_clock(op)) for op in ops[:64]) > 64 for _, ops in batch)
+    caps = og.caps(8, 8, 16, 8, 32, 8)
+    S, E = og.oracle_slabs(oracle, batch, A, caps, caps)
+    _assert_rows(_apply(gpu, S, [ops for _, ops in batch], A, caps), E)
+
+
+# ------------------------------------------------- 5. actor-width boundaries
+@pytest.mark.parametrize("n_actors", [64, 65, 100, 128])
+def test_map_orswot_apply_actor_widths(gpu, oracle, n_actors):
+    """One slot per lane up to 64 actors, two from 65: the last lane of each
+    slot (actors 63, 64, n_actors - 1) carries dots, nested clock entries and
+    rm-clock entries."""
+    batch, S, E = _reference(0xB0 + n_actors, 300, n_actors)
+    for a in {63, n_actors - 1} | ({64} if n_actors > 64 else set()):
+        assert E.a["clock"][:, a].any() and E.a["vclock"][:, :, a].any(), a
+        assert any(op[0] != "rm" and op[1] == a for _, ops in batch for op in ops), a
+        assert any(a in dict(og.op_clock(op)) for _, ops in batch for op in ops), a
+    _assert_rows(_apply(gpu, S, [ops for _, ops in batch], n_actors, OUT_CAPS), E)
+
+
+# -------------------------------- 6. ordered structures past one wave's lanes
+@functools.lru_cache(maxsize=None)
+def _wide_case():
+    """A map of 70 keys, key 350's set holding 70 members and 66 deferred
+    clocks, 66 map deferred clocks, and an op list that edits the front, the
+    middle and the end of each ordered structure."""
+    m = og.new_map()
+    for k in range(70):  # keys 10, 20, .. 700, each {5}
+        og.apply_op(m, ("up_add", 0, k + 1, 10 * (k + 1), 5))
+    for j in range(69):  # key 350: members 5, 10, 20, .. 690
+        og.apply_op(m, ("up_add", 0, 71 + j, 350, 10 * (j + 1)))
+    for d in range(66):  # map deferred [(2, 100)] .. [(2, 165)], each naming the absent key 5
+        og.apply_op(m, ("rm", 5, [(2, 100 + d)]))
+    for d in range(66):  # key 350's deferred [(3, 100)] .. [(3, 165)], each naming the absent member 7
+        og.apply_op(m, ("up_rm", 1, d + 1, 350, 7, [(3, 100 + d)]))
+    o = m.entries[350][1]
+    assert len(m.entries) == 70 and len(o.entries) == 70 and len(m.deferred) == 66 and len(o.deferred) == 66
+    ops = [
+        ("up_add", 4, 1, 1, 5),                          # a key below the first,
+        ("up_add", 4, 2, 355, 5),                        # between two keys,
+        ("up_add", 4, 3, 10000, 5),                      # above the last
+        ("up_add", 4, 4, 350, 1),                        # a member below the first of key 350's set,
+        ("up_add", 4, 5, 350, 355),                      # between two,
+        ("up_add", 4, 6, 350, 10000),                    # above the last
+        ("up_rm", 4, 7, 350, 1, [(4, 4)]),               # the first member removed,
+        ("up_rm", 4, 8, 350, 350, [(0, 105)]),           # a middle one,
+        ("up_rm", 4, 9, 350, 10000, [(4, 6)]),           # the last
+        ("rm", 1, [(4, 1)]),                             # the first entry emptied,
+        ("rm", 355, [(4, 2)]),                           # a middle entry,
+        ("rm", 10000, [(4, 3)]),                         # the last entry
+        ("rm", 20, [(0, 500)]),                          # future clocks: the front of CLOCK ORDER (drops key 20),
+        ("rm", 30, [(2, 130), (3, 1)]),                  # the middle ([(2, 130)] is its proper prefix),
+        ("rm", 20, [(3, 5), (4, 1)]),                    # the end,
+        ("rm", 30, [(3, 5)]),                            # and a proper prefix of the last one, before it
+        ("rm", 2, [(2, 110)]),                           # an existing deferred clock: a key below its set's {5}
+        ("rm", 999, [(2, 110)]),                         # and one above
+        ("up_rm", 4, 10, 350, 7, [(2, 1)]),              # nested deferred clocks: the front,
+        ("up_rm", 4, 11, 350, 7, [(3, 130), (5, 1)]),    # the middle,
+        ("up_rm", 4, 12, 350, 7, [(5, 5), (6, 1)]),      # the end,
+        ("up_rm", 4, 13, 350, 7, [(5, 5)]),              # and a proper prefix of the last one
+        ("up_rm", 4, 14, 350, 3, [(3, 110)]),            # an existing nested deferred clock: a member below {7}
+        ("up_rm", 4, 15, 350, 999, [(3, 110)]),          # and one above
+        ("rm", 40, [(4, 20)]),                           # a map deferred clock
+        ("up_add", 4, 20, 40, 6),                        # and the Up that retires it, and only it
+        ("up_rm", 4, 21, 350, 7, [(4, 30)]),             # a nested deferred clock
+        ("up_add", 4, 30, 350, 8),                       # and the Add that retires it, and only it
+        ("nop",),
+    ]
+    return m, ops
+
+
+WIDE_IN, WIDE_OUT = og.caps(80, 80, 72, 4, 72, 4), og.caps(80, 80, 80, 4, 80, 4)
+
+
+def test_map_orswot_apply_wide_ordered_structures(gpu):
+    m, ops = _wide_case()
+    S = _row_slab(m, A, WIDE_IN)
+    # the whole list in one call
+    exp = m.clone()
+    for op in ops:
+        og.apply_op(exp, op)
+    o = exp.entries[350][1]
+    assert len(exp.deferred) == 66 + 4 and len(exp.entries) == 69  # ([(0, 500)] also empties key 20's entry)
+    assert len(o.deferred) == 66 + 4 and sorted(o.deferred[crdts_ref.VClock([(3, 110)])]) == [3, 7, 999]
+    assert sorted(exp.deferred[crdts_ref.VClock([(2, 110)])]) == [2, 5, 999]
+    assert len(o.entries) == 71 and 350 not in o.entries and 355 in o.entries and 8 in o.entries
+    _assert_rows(_apply(gpu, S, [ops], A, WIDE_OUT), _row_slab(exp, A, WIDE_OUT), what="one call")
+    # and every prefix of the list, as one batch (the states are not chained:
+    # a map past the input capacities is no input of the call)
+    import crdts_hip
+
+    n = len(ops)
+    Sn = crdts_hip.MapOrswotSlab({f: np.repeat(v, n, axis=0) for f, v in S.a.items()}, WIDE_IN)
+    E = crdts_hip.MapOrswotSlab.alloc(n, A, **WIDE_OUT)
+    py = m.clone()
+    for t, op in enumerate(ops):
+        before, vbefore = len(py.deferred), len(py.entries[350][1].deferred)
+        og.apply_op(py, op)
+        if t == 25:
+            assert before == 71 and len(py.deferred) == 70  # the Up retired one map deferred clock
+        if t == 27:
+            assert vbefore == 71 and len(py.entries[350][1].deferred) == 70  # the Add retired one nested one
+        map_slab.orswot_map_to_row(py, E, t, A)
+    _assert_rows(_apply(gpu, Sn, [ops[:t + 1] for t in range(n)], A, WIDE_OUT), E, what="prefixes")
+
+
+def test_map_orswot_apply_across_64_keys(gpu):
+    """A map that grows from 63 keys past 64 and shrinks back below: the kernel
+    searches a copy of the keys held in LDS up to 64 keys and the output row
+    itself from the 65th on. The whole list and every prefix."""
+    import crdts_hip
+
+    m = og.new_map()
+    for k in range(63):  # keys 10, 20, .. 630
+        og.apply_op(m, ("up_add", 0, k + 1, 10 * (k + 1), 5))
+    ops = [("up_add", 4, 1, 5, 1),        # the 64th key, below the first
+           ("up_add", 4, 2, 5, 2),        # (found through the copy)
+           ("up_add", 4, 3, 635, 1),      # the 65th, above the last
+           ("up_add", 4, 4, 7, 1),        # the 66th, in the second slot
+           ("up_rm", 4, 5, 635, 1, [(4, 3)]),
+           ("rm", 5, [(4, 2)]), ("rm", 7, [(4, 4)]), ("rm", 635, [(4, 5)]), ("rm", 10, [(0, 1)]),  # back to 62
+           ("up_add", 4, 6, 20, 9),       # an old key, a new one
+           ("up_add", 4, 7, 1, 9)]
+    caps = og.caps(72, 4, 4, 4, 4, 4)
+    n = len(ops)
+    S = _row_slab(m, A, caps)
+    Sn = crdts_hip.MapOrswotSlab({f: np.repeat(v, n, axis=0) for f, v in S.a.items()}, caps)
+    E = crdts_hip.MapOrswotSlab.alloc(n, A, **caps)
+    py, sizes = m.clone(), []
+    for t, op in enumerate(ops):
+        og.apply_op(py, op)
+        sizes.append(len(py.entries))
+        map_slab.orswot_map_to_row(py, E, t, A)
+    assert sizes == [64, 64, 65, 66, 66, 65, 64, 63, 62, 62, 63]
+    _assert_rows(_apply(gpu, Sn, [ops[:t + 1] for t in range(n)], A, caps), E)
+
+
+# ------------------------------------------------ 7. the hand-built cases
+def test_map_orswot_apply_hand_built_cases(gpu, oracle):
+    """(a) a nested Rm that leaves a smaller non-empty member clock; (b) a
+    nested duplicate dot under a fresh map dot; (c) the case whose result
+    depends on apply_deferred's order: the kernel gives the CLOCK ORDER one."""
+    import crdts_hip
+
+    cases = [(og.new_map(), og.CASE_A), (og.case_b_map(), [og.CASE_B_OP]), (og.new_map(), og.CASE_C)]
+    S = crdts_hip.MapOrswotSlab.alloc(len(cases), A, **IN_CAPS)
+    E = crdts_hip.MapOrswotSlab.alloc(len(cases), A, **OUT_CAPS)
+    e = E.cstruct()
+    for i, (m, ops) in enumerate(cases):
+        map_slab.orswot_map_to_row(m, S, i, A)
+        h = og.oracle_from_row(oracle, S, i, A)
+        py = m.clone()
+        for op in ops:
+            og.apply_op_oracle(h, op)
+            og.apply_op(py, op)
+        assert oracle.lib().orc_mapor_to_slab(h.h, C.byref(e), i, A) == 0
+        assert map_slab.orswot_map_from_row(E, i) == py
+    assert map_slab.orswot_map_from_row(E, 0).entries[7][1].entries == {1: crdts_ref.VClock([(1, 1)])}
+    assert len(map_slab.orswot_map_from_row(E, 2).entries[7][1].deferred) == 2
+    _assert_rows(_apply(gpu, S, [ops for _, ops in cases], A, OUT_CAPS), E)
+    # (c) op by op as well: each output the next input
+    cur = crdts_hip.MapOrswotSlab.alloc(1, A, **IN_CAPS)
+    py = og.new_map()
+    for t, op in enumerate(og.CASE_C):
+        cur = _apply(gpu, cur, [[op]], A, IN_CAPS).host()
+        og.apply_op(py, op)
+        assert map_slab.orswot_map_from_row(cur, 0) == py, t
+
+
+# ------------------------------------------------ 8. copy-through and empties
+def test_map_orswot_apply_copy_through_and_empties(gpu, oracle):
+    import crdts_hip
+
+    gen = og.gen_batch(0xE1, 8, A)
+    full = lambda i: gen[i][0] + gen[i][1]  # noqa: E731
+    batch = [(full(0), gen[1][1]),            # a map with ops
+             (full(2), []),                   # no ops, between two that have some
+             (full(3), gen[4][1]),
+             ([], [("nop",)] + full(5)),      # an all-empty self map
+             ([], [])]                        # empty map, no ops
+    S, E = og.oracle_slabs(oracle, batch, A, IN_CAPS, OUT_CAPS)
+    assert S.a["n_keys"][1] > 0 and S.a["n_keys"][3] == 0 and not S.a["clock"][3].any()
+    _assert_rows(_apply(gpu, S, [ops for _, ops in batch], A, OUT_CAPS), E)
+    # n_ops == 0: null op arrays, every object copied through
+    none = crdts_hip.MapOrswotOps.from_lists([[] for _ in batch])
+    assert none.n_ops == 0 and none.cops().kind is None and none.cops().clk_act is None
+    W = crdts_hip.MapOrswotSlab({f: v.copy() for f, v in S.a.items()}, IN_CAPS)
+    _assert_rows(_apply(gpu, S, none, A, IN_CAPS), W)
+    # n_obj == 0
+    Z = crdts_hip.MapOrswotSlab.alloc(0, A, **IN_CAPS)
+    out = gpu.map_orswot_apply(Z.to("cuda"), crdts_hip.MapOrswotOps.from_lists([]), A, out_caps=OUT_CAPS)
+    assert out.n == 0
+
+
+# ------------------------------------------------------------------ 9. capacity
+def _overflowing(which):
+    """An op list that needs 5 slots of `which` (out capacity 4) at its 5th op."""
+    if which == "kcap":
+        return [("up_add", 0, k + 1, 100 + k, 1) for k in range(5)]
+    if which == "mcap":  # five members of one key
+        return [("up_add", 0, k + 1, 7, 100 + k) for k in range(5)]
+    if which == "vdcap":  # five future clocks in one key's set
+        return [("up_rm", 0, d + 1, 7, 1, [(3, 10 + d)]) for d in range(5)]
+    if which == "vscap":  # five members under one future clock
+        return [("up_rm", 0, k + 1, 7, 100 + k, [(3, 10)]) for k in range(5)]
+    if which == "dcap":  # five future clocks
+        return [("rm", 7, [(3, 10 + d)]) for d in range(5)]
+    if which == "scap":  # five keys under one future clock
+        return [("rm", 100 + k, [(3, 10)]) for k in range(5)]
+    # kcap, intermediate only: four keys, then a fifth whose fresh entry the
+    # deferred remove takes away within its own Up — it still needs its slot
+    return [("up_add", 0, k + 1, 100 + k, 1) for k in range(4)] + [("rm", 200, [(1, 1)]), ("up_add", 1, 1, 200, 1)]
+
+
+@pytest.mark.parametrize("which", list(og.CAP_NAMES) + ["kcap_intermediate"])
+def test_map_orswot_apply_capacity(gpu, oracle, which):
+    import crdts_hip
+
+    gen = og.gen_batch(0x0A57, 2, A)
+    caps = {c: 4 if c == which.split("_")[0] else 8 for c in og.CAP_NAMES}
+    over = _overflowing(which)
+    fits = over[:-1]
+    S, E = og.oracle_slabs(oracle, [gen[0], ([], fits), gen[1]], A, IN_CAPS, caps)
+    if which == "kcap_intermediate":  # the final state itself fits
+        og.oracle_slabs(oracle, [([], over)], A, IN_CAPS, caps)
+    # all but the last op fit: the status is clean and the row exact
+    _assert_rows(_apply(gpu, S, [gen[0][1], fits, gen[1][1]], A, caps), E)
+    with pytest.raises(crdts_hip.CrdtError) as e:
+        _apply(gpu, S, [gen[0][1], over, gen[1][1]], A, caps)
+    assert e.value.code == crdts_hip.CRDT_ECAPACITY
+    got = _apply(gpu, S, [gen[0][1], over, gen[1][1]], A, caps, check_status=False)
+    with pytest.raises(crdts_hip.CrdtError):
+        gpu.status()
+    _assert_rows(got, E, rows=[0, 2], what="neighbours")
+    gpu.status()  # the latch is cleared: the context is usable again
+
+
+# ------------------------------------------------------------------ 10. non-canonical
+def _raw_ops(per_obj, **patch):
+    import crdts_hip
+
+    names = ("obj_end", "kind", "key", "actor", "counter", "member", "clk_end", "clk_act", "clk_ctr")
+    arrs = dict(zip(names, crdts_hip.MapOrswotOps.arrays_from_lists(per_obj)))
+    for k, v in patch.items():
+        arrs[k] = np.asarray(v, dtype=arrs[k].dtype)
+    return crdts_hip.MapOrswotOps.from_arrays(*(arrs[k] for k in names))
+
+
+GOOD = [("up_rm", 0, 1, 7, 5, [(0, 1)])]
+NONCANON = {
+    "descending_clock_actors": lambda: _raw_ops([GOOD, [("rm", 3, [(2, 1), (1, 1)])], GOOD]),
+    "equal_clock_actors": lambda: _raw_ops([GOOD, [("up_rm", 1, 1, 3, 5, [(2, 1), (2, 2)])], GOOD]),
+    "zero_counter": lambda: _raw_ops([GOOD, [("rm", 3, [(1, 0)])], GOOD]),
+    "clock_actor_out_of_range": lambda: _raw_ops([GOOD, [("up_rm", 1, 1, 3, 5, [(A, 1)])], GOOD]),
+    "dot_actor_out_of_range": lambda: _raw_ops([GOOD, [("up_add", A, 1, 3, 5)], GOOD]),
+    "kind_4": lambda: _raw_ops([GOOD, [("nop",)], GOOD], kind=[3, 4, 3]),
+    "decreasing_obj_end": lambda: _raw_ops([GOOD, GOOD, GOOD], obj_end=[2, 1, 3]),
+    "obj_end_past_n_ops": lambda: _raw_ops([GOOD, GOOD, GOOD], obj_end=[1, 9, 3]),
+    "clk_end_past_n_clk": lambda: _raw_ops([GOOD, GOOD, GOOD], clk_end=[1, 7, 3]),
+}
+
+
+@pytest.mark.parametrize("name", sorted(NONCANON))
+def test_map_orswot_apply_noncanonical_ops(gpu, name):
+    """A malformed op list latches CRDT_ENONCANON for its object; the first
+    object of the batch, whose list is well formed, is exact."""
+    import crdts_hip
+
+    S = crdts_hip.MapOrswotSlab.alloc(3, A, **IN_CAPS)
+    exp = og.new_map()
+    og.apply_op(exp, GOOD[0])
+    E = crdts_hip.MapOrswotSlab.alloc(3, A, **OUT_CAPS)
+    map_slab.orswot_map_to_row(exp, E, 0, A)
+    got = _apply(gpu, S, NONCANON[name](), A, OUT_CAPS, check_status=False)
+    with pytest.raises(crdts_hip.CrdtError) as e:
+        gpu.status()
+    assert e.value.code == crdts_hip.CRDT_ENONCANON
+    _assert_rows(got, E, rows=[0], what=name)
+    gpu.status()
+
+
+def test_map_orswot_apply_noncanonical_input_row(gpu):
+    """An input row the merge rejects: a member count above mcap."""
+    m = og.new_map()
+    og.apply_op(m, ("up_add", 0, 1, 7, 5))
+    S = _row_slab(m, A, IN_CAPS)
+    S.a["vn_mem"][0, 0] = IN_CAPS["mcap"] + 1
+    import crdts_hip
+
+    with pytest.raises(crdts_hip.CrdtError) as e:
+        _apply(gpu, S, [[]], A, OUT_CAPS)
+    assert e.value.code == crdts_hip.CRDT_ENONCANON
+
+
+# ------------------------------------------------------------------ 11. EINVAL
+def test_map_orswot_apply_einval(gpu):
+    import crdts_hip
+
+    S = crdts_hip.MapOrswotSlab.alloc(1, A, **IN_CAPS).to("cuda")
+    ops = crdts_hip.MapOrswotOps.from_lists([GOOD])
+    for kw in (dict(n_actors=129, out_caps=OUT_CAPS), dict(n_actors=A, out_caps=dict(OUT_CAPS, kcap=3)),
+               dict(n_actors=A, out_caps=dict(OUT_CAPS, vscap=3)), dict(n_actors=A, out_caps=dict(OUT_CAPS, kcap=8200)),
+               dict(n_actors=A, out_caps=dict(OUT_CAPS, dcap=513)), dict(n_actors=A, out=S)):
+        with pytest.raises(crdts_hip.CrdtError) as e:
+            gpu.map_orswot_apply(S, ops, **kw)
+        assert e.value.code == crdts_hip.CRDT_EINVAL, kw
+    gpu.status()
