@@ -623,6 +623,104 @@ int crdt_map_map_merge(crdt_ctx* ctx, const crdt_map_map_slab* self, const crdt_
                        size_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * Map<K, Map<K, MVReg<u64, A>, A>, A>::apply (CmRDT), batched — the op path
+ * of TestMap: out[i] := self[i] after Map::apply (src/map.rs:160-190) of each
+ * of object i's ops, in order, in the slab's canonical form (outer and inner:
+ * keys ascending, MVReg values in Vec order, deferred clocks in CLOCK ORDER,
+ * deferred key sets ascending). Only the used slots of out are written (the
+ * inner rows of unused key slots not at all). Object i's ops are
+ * [obj_end[i-1], obj_end[i]) of the op arrays (all device arrays); op j's
+ * clock — an outer Rm's clock, an inner Rm's clock, an inner Up's Put clock —
+ * is the pairs [clk_end[j-1], clk_end[j]) of clk_act / clk_ctr, actors
+ * strictly increasing, counters non-zero. The inner Up's dot (actor2,
+ * counter2) is a field of its own: Map::update makes it the outer dot, but
+ * nothing in apply requires that.
+ *
+ * The reference's rules, as applied:
+ *  - Op::Nop (:165): nothing.
+ *  - Outer Op::Up, duplicate dot (:170-173): if map.clock.get(actor) >=
+ *    counter the WHOLE op is skipped — no inner apply, no apply_deferred.
+ *  - Outer Op::Up otherwise (:175-187): the entry is taken out, or starts from
+ *    an empty clock and an empty inner map; entry.clock.witness(dot); the
+ *    inner op runs on the inner map by the same Map::apply, against the inner
+ *    map's own clock:
+ *      inner Nop leaves it alone (a fresh key then holds an empty inner map,
+ *        a legal state);
+ *      inner Rm is the inner apply_rm (:336-350) with MVReg::truncate
+ *        (src/mvreg.rs:100-113);
+ *      inner Up is skipped when the inner clock has dot2 (:170-173; the outer
+ *        op still counts), else the inner entry witnesses dot2 and takes the
+ *        Put (src/mvreg.rs:158-186; an empty Put clock leaves the values
+ *        untouched), the inner clock witnesses dot2 and the inner
+ *        apply_deferred (:325-333) runs;
+ *    the entry goes back in; map.clock.witness(dot); the outer apply_deferred.
+ *  - Outer Op::Rm, and every step of the outer apply_deferred -> apply_rm
+ *    (:336-350): if !(clock <= map.clock) it is deferred — the key joins an
+ *    equal deferred clock's set, or a new entry is inserted at its CLOCK ORDER
+ *    place; then, if the entry exists, clock is subtracted from its clock and
+ *    an emptied entry is dropped, else the inner map takes
+ *    Map::truncate(clock) (:131-158): each inner entry clock is subtracted, an
+ *    emptied inner entry is dropped and any other takes MVReg::truncate; every
+ *    inner deferred clock is subtracted and an emptied one is dropped; the
+ *    inner clock is subtracted. An empty Rm clock changes nothing.
+ *  - Inner deferred clocks under Map::truncate (:147-154): the subtract can
+ *    reorder them and can make two equal; the result is put back in CLOCK
+ *    ORDER, and where two become equal the key set of the later one (CLOCK
+ *    ORDER before the subtract) is kept, as in crdt_map_map_merge (the
+ *    reference inserts into a HashMap there).
+ *  - The outer apply_deferred walks CLOCK ORDER, keys ascending. Apart from
+ *    the collapse above the order is free: every step is a subtract.
+ *
+ * d_scratch: crdt_map_map_apply_scratch_bytes(out, n_obj, n_actors) bytes,
+ * 16-byte aligned (an inner slab like out's, in which the edited inner maps
+ * live until they are placed, and the per-key-slot placement tasks).
+ *
+ * CRDT_EINVAL (before any device work): a null ctx / self / ops / out;
+ * n_actors == 0 or > 128; self capacities outside crdt_map_map_merge's
+ * per-side limits (outer kcap 4096, dcap 64, scap 4096; inner kcap 4096, mcap
+ * 128, dcap 64, scap 4096); an out capacity below self's or above twice that
+ * limit, outer or inner; a null slab array or a null, misaligned or too small
+ * scratch with n_obj > 0; a null op array its count says is non-empty
+ * (obj_end: n_obj; kind .. clk_end: n_ops; clk_act, clk_ctr: n_clk);
+ * out->clock == self->clock (the call is not in place, and no out array may
+ * overlap a self array). n_obj == 0 is CRDT_OK; an object without ops is
+ * copied through.
+ * Latched per object (the other objects are unaffected, the object's output
+ * row is unspecified): CRDT_ECAPACITY when at any step of its op list —
+ * intermediate states count — the state needs more than one of out's seven
+ * capacities; CRDT_ENONCANON for an input row the merge rejects (a count
+ * above its capacity, outer or inner), obj_end / clk_end decreasing or past
+ * n_ops / n_clk (nothing outside the op arrays is read), an unknown kind, an
+ * actor >= n_actors in the dot, in an UP_UP's inner dot or in a clock, an op
+ * clock whose actors are not strictly increasing or that holds a zero
+ * counter.                                                                   */
+#define CRDT_MAPMAP_OP_NOP 0u    /* Op::Nop */
+#define CRDT_MAPMAP_OP_RM 1u     /* Op::Rm { clock, key } */
+#define CRDT_MAPMAP_OP_UP_UP 2u  /* Op::Up { dot, key, op: Op::Up { dot2, key2, op: Put { clock, val } } } */
+#define CRDT_MAPMAP_OP_UP_RM 3u  /* Op::Up { dot, key, op: Op::Rm { clock, key2 } } */
+#define CRDT_MAPMAP_OP_UP_NOP 4u /* Op::Up { dot, key, op: Op::Nop } */
+typedef struct crdt_map_map_ops {
+  const uint64_t* obj_end;   /* device, n_obj */
+  const uint32_t* kind;      /* device, n_ops */
+  const uint64_t* key;       /* device, n_ops: the outer key (Rm, Up) */
+  const uint32_t* actor;     /* device, n_ops: the outer dot (Up) */
+  const uint64_t* counter;   /* device, n_ops */
+  const uint64_t* key2;      /* device, n_ops: the inner key (UP_UP, UP_RM) */
+  const uint32_t* actor2;    /* device, n_ops: the inner dot (UP_UP) */
+  const uint64_t* counter2;  /* device, n_ops */
+  const uint64_t* val;       /* device, n_ops: the Put's value (UP_UP) */
+  const uint64_t* clk_end;   /* device, n_ops */
+  const uint32_t* clk_act;   /* device, n_clk */
+  const uint64_t* clk_ctr;   /* device, n_clk */
+  size_t n_ops;
+  size_t n_clk;
+} crdt_map_map_ops;
+size_t crdt_map_map_apply_scratch_bytes(const crdt_map_map_slab* out, size_t n_obj, uint32_t n_actors);
+int crdt_map_map_apply(crdt_ctx* ctx, const crdt_map_map_slab* self, const crdt_map_map_ops* ops,
+                       const crdt_map_map_slab* out, size_t n_obj, uint32_t n_actors, void* d_scratch,
+                       size_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * Map<K, Orswot<u64, A>, A>::merge, batched (SURVEY.md §8(f) rank 3 as
  * written: src/map.rs:192-269 with the nested value's Causal::truncate,
  * src/orswot.rs:159-172, and Orswot::merge src/orswot.rs:87-157 for keys in

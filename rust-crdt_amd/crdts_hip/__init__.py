@@ -25,7 +25,7 @@ __all__ = [
     "Engine", "OrswotBatch", "GenParams", "CrdtError", "generate_orswot", "generate_dense", "HostOrswot",
     "Orswot", "VClock", "GCounter", "PNCounter", "merge_batch", "decode_record", "encode_record",
     "record_bytes", "CONFIG3", "EXPORTS", "LIB_PATH", "CONFIG5", "SPARSE_CLOCK", "generate_replicas", "ClockBatch",
-    "generate_clocks_csr", "MapMapSlab", "MapOps",
+    "generate_clocks_csr", "MapMapSlab", "MapOps", "MapMapOps",
 ]
 
 # SURVEY.md §8(d) config 3 / BASELINE.json configs[2].
@@ -273,6 +273,91 @@ class MapOps:
     @classmethod
     def from_lists(cls, per_obj, device=0):
         """per_obj[i] = [("up", actor, counter, key, [(a, c), ...], val) | ("rm", key, [(a, c), ...]) | ("nop",), ...]"""
+        return cls.from_arrays(*cls.arrays_from_lists(per_obj), device=device)
+
+
+class MapMapOps:
+    """A batch of Map<u64, Map<u64, MVReg<u64, A>, A>, A> ops (the reference's
+    TestMap: Op::Nop / Op::Rm / Op::Up whose inner op is again a Map op,
+    src/map.rs:104-125) on the device, grouped per object in order
+    (crdt_map_map_ops). Ops are given in their literal JSON form:
+
+        "nop"
+        {"rm": {"clock": [[a, c], ...], "key": k}}
+        {"up": {"dot": [a, c], "key": k, "op": INNER}}
+        INNER = "nop" | {"rm": {"clock": [...], "key": k2}}
+              | {"up": {"dot": [a2, c2], "key": k2, "op": {"put": {"clock": [...], "val": v}}}}"""
+
+    NOP, RM, UP_UP, UP_RM, UP_NOP = 0, 1, 2, 3, 4
+    FIELDS = ("obj_end", "kind", "key", "actor", "counter", "key2", "actor2", "counter2", "val", "clk_end", "clk_act",
+              "clk_ctr")
+    U32 = ("kind", "actor", "actor2", "clk_act")
+
+    def __init__(self, *tensors):
+        assert len(tensors) == len(self.FIELDS)
+        self.t = tuple(tensors)
+        self.n_obj = int(tensors[0].numel())
+        self.n_ops = int(tensors[1].numel())
+        self.n_clk = int(tensors[10].numel())
+
+    def cops(self):
+        from ._lib import MapMapOpsC
+
+        p = [C.c_void_p(t.data_ptr()) if t.numel() else None for t in self.t]
+        return MapMapOpsC(*p, self.n_ops, self.n_clk)
+
+    @classmethod
+    def from_arrays(cls, *arrays, device=0):
+        """The twelve host numpy arrays (u64 / u32 as in crdt_map_map_ops, in FIELDS order) -> device."""
+        torch = _torch()
+        dev = f"cuda:{device}"
+        out = []
+        for f, x in zip(cls.FIELDS, arrays):
+            u32 = f in cls.U32
+            x = np.ascontiguousarray(np.asarray(x, dtype=np.uint32 if u32 else np.uint64))
+            out.append(torch.from_numpy(x.view(np.int32 if u32 else np.int64)).to(dev))
+        return cls(*out)
+
+    @staticmethod
+    def arrays_from_lists(per_obj):
+        """per_obj[i] = the object's ops in their JSON form -> the twelve host
+        arrays of crdt_map_map_ops, in FIELDS order. Fields an op does not
+        have are 0; an op's clock pairs are the outer Rm's clock, the inner
+        Rm's clock or the inner Up's Put clock."""
+        a = {f: [] for f in MapMapOps.FIELDS}
+        for ops in per_obj:
+            for op in ops:
+                kind, key, dot, key2, dot2, val, pairs = MapMapOps.NOP, 0, (0, 0), 0, (0, 0), 0, ()
+                if op == "nop":
+                    pass
+                elif "rm" in op:
+                    kind, key, pairs = MapMapOps.RM, op["rm"]["key"], op["rm"]["clock"]
+                elif "up" in op:
+                    up = op["up"]
+                    key, dot, inner = up["key"], up["dot"], up["op"]
+                    if inner == "nop":
+                        kind = MapMapOps.UP_NOP
+                    elif "rm" in inner:
+                        kind, key2, pairs = MapMapOps.UP_RM, inner["rm"]["key"], inner["rm"]["clock"]
+                    elif "up" in inner:
+                        put = inner["up"]["op"]["put"]
+                        kind, key2, dot2 = MapMapOps.UP_UP, inner["up"]["key"], inner["up"]["dot"]
+                        val, pairs = put["val"], put["clock"]
+                    else:
+                        raise ValueError(f"unknown inner map op {inner!r}")
+                else:
+                    raise ValueError(f"unknown map op {op!r}")
+                a["kind"].append(kind); a["key"].append(key); a["actor"].append(dot[0]); a["counter"].append(dot[1])
+                a["key2"].append(key2); a["actor2"].append(dot2[0]); a["counter2"].append(dot2[1]); a["val"].append(val)
+                for x, c in pairs:
+                    a["clk_act"].append(x); a["clk_ctr"].append(c)
+                a["clk_end"].append(len(a["clk_act"]))
+            a["obj_end"].append(len(a["kind"]))
+        return tuple(np.asarray(a[f], np.uint32 if f in MapMapOps.U32 else np.uint64) for f in MapMapOps.FIELDS)
+
+    @classmethod
+    def from_lists(cls, per_obj, device=0):
+        """per_obj[i] = the object's ops in their JSON form, as for arrays_from_lists."""
         return cls.from_arrays(*cls.arrays_from_lists(per_obj), device=device)
 
 
@@ -953,6 +1038,43 @@ class Engine:
         if check_status:
             self.status(stream)
         return R
+
+    MAP_MAP_APPLY_CAP_MAX = ((8192, 128, 8192), (8192, 256, 128, 8192))  # outer (k, d, s), inner (k, m, d, s)
+
+    def map_map_apply(self, S: "MapMapSlab", ops: "MapMapOps", n_actors, out_caps=None, inner_out_caps=None,
+                      out=None, stream=None, check_status=True):
+        """out[i] = S[i] after Map::apply (src/map.rs:160-190, the inner op by
+        the same apply on the inner map) of object i's ops in order; returns
+        the output slab (`out`, or a new one of capacities out_caps = (kcap,
+        dcap, scap) and inner_out_caps = (kcap, mcap, dcap, scap), default:
+        S's plus one slot per op of the longest op list, within the call's
+        limits). Only the used slots of the output are written. Not in place."""
+        torch = _torch()
+        n = S.n
+        dev = S.a["clock"].device
+        if out is None:
+            if out_caps is None or inner_out_caps is None:
+                ends = ops.t[0].cpu().numpy().view(np.uint64) if ops.n_obj else np.zeros(0, np.uint64)
+                grow = int(np.diff(ends, prepend=np.uint64(0)).max()) if ends.size else 0
+                mo, mi = self.MAP_MAP_APPLY_CAP_MAX
+                if out_caps is None:
+                    out_caps = tuple(min(m, c + grow) for m, c in zip(mo, (S.kcap, S.dcap, S.scap)))
+                if inner_out_caps is None:
+                    inner_out_caps = tuple(min(m, c + grow) for m, c in zip(mi, S.inner_caps))
+            out = MapMapSlab.alloc(n, n_actors, *out_caps, tuple(inner_out_caps), device=dev)
+        s, o, r = S.cstruct(), ops.cops(), out.cstruct()
+        nb = int(lib.crdt_map_map_apply_scratch_bytes(C.byref(r), n, n_actors))
+        # the engine keeps the scratch (grown as needed): a launch in flight on
+        # another stream never sees it freed
+        sc = getattr(self, "_map_map_apply_scratch", None)
+        if sc is None or sc.numel() < nb or sc.device != dev:
+            sc = self._map_map_apply_scratch = torch.empty(max(16, nb), dtype=torch.uint8, device=dev)
+        check(lib.crdt_map_map_apply(self.ctx, C.byref(s), C.byref(o), C.byref(r), n, n_actors,
+                                     C.c_void_p(sc.data_ptr()), int(sc.numel()), self._stream(stream)),
+              "map_map_apply")
+        if check_status:
+            self.status(stream)
+        return out
 
     # ------------------------------------------------ Map<u64, Orswot<u64>>
     def map_orswot_merge(self, S: "MapOrswotSlab", O: "MapOrswotSlab", n_actors, out_caps=None, stream=None,

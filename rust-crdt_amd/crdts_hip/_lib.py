@@ -78,6 +78,7 @@ EXPORTS = [
     "crdt_orswot_truncate", "crdt_ctx_host_syncs", "crdt_orswot_fold", "crdt_ctx_set_arena_limit",
     "crdt_map_map_merge_scratch_bytes", "crdt_map_map_merge", "crdt_replica_allreduce_max_transport",
     "crdt_replica_reduce_scatter_max_transport", "crdt_map_mvreg_apply", "crdt_map_orswot_apply",
+    "crdt_map_map_apply_scratch_bytes", "crdt_map_map_apply",
 ]
 
 CRDT_COMM_ID_BYTES = 128
@@ -109,6 +110,15 @@ class MapOpsC(C.Structure):
     """crdt_map_mvreg_ops (include/crdts_hip.h)."""
     _fields_ = [(f, C.c_void_p) for f in ("obj_end", "kind", "key", "actor", "counter", "val", "clk_end", "clk_act",
                                           "clk_ctr")] + [("n_ops", C.c_size_t), ("n_clk", C.c_size_t)]
+
+
+MAP_MAP_OPS_FIELDS = ("obj_end", "kind", "key", "actor", "counter", "key2", "actor2", "counter2", "val", "clk_end",
+                      "clk_act", "clk_ctr")
+
+
+class MapMapOpsC(C.Structure):
+    """crdt_map_map_ops (include/crdts_hip.h)."""
+    _fields_ = [(f, C.c_void_p) for f in MAP_MAP_OPS_FIELDS] + [("n_ops", C.c_size_t), ("n_clk", C.c_size_t)]
 
 
 class MapOrswotOpsC(C.Structure):
@@ -241,6 +251,9 @@ def _load():
                                       C.POINTER(MapOrswotSlabC), SZ, U32, P]),
         "crdt_map_map_merge_scratch_bytes": (SZ, [C.POINTER(MapMapSlabC), SZ, U32]),
         "crdt_map_map_merge": (I, [P, C.POINTER(MapMapSlabC), C.POINTER(MapMapSlabC), C.POINTER(MapMapSlabC), SZ,
+                                   U32, P, SZ, P]),
+        "crdt_map_map_apply_scratch_bytes": (SZ, [C.POINTER(MapMapSlabC), SZ, U32]),
+        "crdt_map_map_apply": (I, [P, C.POINTER(MapMapSlabC), C.POINTER(MapMapOpsC), C.POINTER(MapMapSlabC), SZ,
                                    U32, P, SZ, P]),
         "crdt_comm_unique_id": (I, [P]),
         "crdt_comm_init": (I, [P, P, I, I]),

@@ -651,6 +651,48 @@ int crdt_map_map_merge(crdt_ctx* ctx, const crdt_map_map_slab* self, const crdt_
                               S(stream));
 }
 
+static bool map_map_ptrs_ok(const crdt_map_map_slab* x) {
+  return x->clock && x->n_keys && x->keys && x->eclock && x->n_def && x->dclock && x->dset_n && x->dset &&
+         map_mvreg_ptrs_ok(&x->inner);
+}
+// out capacities of the nested apply: >= self's, <= twice the merge's per-side limits
+static bool map_map_apply_caps_ok(const crdt_map_map_slab* self, const crdt_map_map_slab* out) {
+  const crdt_map_mvreg_slab &si = self->inner, &ri = out->inner;
+  if (self->kcap == 0 || self->kcap > 4096 || self->dcap == 0 || self->dcap > 64 || self->scap == 0 ||
+      self->scap > 4096 || !map_mvreg_caps_ok(&si))
+    return false;
+  return out->kcap >= self->kcap && out->kcap <= 8192 && out->dcap >= self->dcap && out->dcap <= 128 &&
+         out->scap >= self->scap && out->scap <= 8192 && ri.kcap >= si.kcap && ri.kcap <= 8192 &&
+         ri.mcap >= si.mcap && ri.mcap <= 256 && ri.dcap >= si.dcap && ri.dcap <= 128 && ri.scap >= si.scap &&
+         ri.scap <= 8192;
+}
+
+size_t crdt_map_map_apply_scratch_bytes(const crdt_map_map_slab* out, size_t n_obj, uint32_t n_actors) {
+  return out ? map_map_apply_scratch_bytes(*out, n_obj, n_actors) : 0u;
+}
+
+int crdt_map_map_apply(crdt_ctx* ctx, const crdt_map_map_slab* self, const crdt_map_map_ops* ops,
+                       const crdt_map_map_slab* out, size_t n_obj, uint32_t n_actors, void* d_scratch,
+                       size_t scratch_bytes, void* stream) {
+  if (!ctx || !self || !ops || !out || n_actors == 0 || n_actors > 128) return CRDT_EINVAL;
+  if (!map_map_apply_caps_ok(self, out)) return CRDT_EINVAL;
+  if (n_obj) {
+    if (!map_map_ptrs_ok(self) || !map_map_ptrs_ok(out) || !ops->obj_end) return CRDT_EINVAL;
+    if (out->clock == self->clock || out->inner.clock == self->inner.clock) return CRDT_EINVAL;  // not in place
+    if (!d_scratch || ((uintptr_t)d_scratch & 15u) ||
+        scratch_bytes < map_map_apply_scratch_bytes(*out, n_obj, n_actors))
+      return CRDT_EINVAL;
+  }
+  if (ops->n_ops && (!ops->kind || !ops->key || !ops->actor || !ops->counter || !ops->key2 || !ops->actor2 ||
+                     !ops->counter2 || !ops->val || !ops->clk_end))
+    return CRDT_EINVAL;
+  if (ops->n_clk && (!ops->clk_act || !ops->clk_ctr)) return CRDT_EINVAL;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_map_map_apply(*self, *ops, *out, n_obj, n_actors, (uint8_t*)d_scratch, ctx->d_status, ctx->d_ctl,
+                              S(stream));
+}
+
 int crdt_map_orswot_merge(crdt_ctx* ctx, const crdt_map_orswot_slab* self, const crdt_map_orswot_slab* other,
                           const crdt_map_orswot_slab* out, size_t n_obj, uint32_t n_actors, void* stream) {
   if (!ctx || !self || !other || !out || n_actors == 0 || n_actors > 128) return CRDT_EINVAL;

@@ -222,7 +222,7 @@ void gen_pair(uint64_t seed, uint64_t obj, const crdt_orswot_gen_params& P, HOrs
   std::vector<uint64_t> base(A);
   for (uint32_t a = 0; a < A; ++a) base[a] = rng.next() & ((1ull << 40) - 1);
   auto next_ctr = [&](const HOrswot& o, uint32_t a) {
-    return std::max(o.clock.get(a), base[a]) + 1;  // derive_add_ctx, src/ctx.rs:599-607
+    return std::max(o.clock.get(a), base[a]) + 1;  // derive_add_ctx, src/ctx.rs:45-53
   };
   // Ancestor: `ancestor_adds` adds of distinct members while the universe
   // lasts (a random permutation), by random actors.
@@ -301,7 +301,7 @@ void gen_replicas(uint64_t seed, uint64_t obj, const crdt_orswot_rep_params& P, 
   auto next_ctr = [&](const HOrswot& o, uint32_t a) {
     auto it = base.find(a);
     if (it == base.end()) it = base.emplace(a, rng.next() & ((1ull << 40) - 1)).first;
-    return std::max(o.clock.get(a), it->second) + 1;  // derive_add_ctx, src/ctx.rs:599-607
+    return std::max(o.clock.get(a), it->second) + 1;  // derive_add_ctx, src/ctx.rs:45-53
   };
   std::vector<uint32_t> perm(U);
   for (uint32_t j = 0; j < U; ++j) perm[j] = j;

@@ -93,6 +93,13 @@ size_t map_map_scratch_bytes(const crdt_map_map_slab& R, uint64_t n_obj, uint32_
 int launch_map_map_merge(const crdt_map_map_slab& S, const crdt_map_map_slab& O, const crdt_map_map_slab& R,
                          uint64_t n_obj, uint32_t A, uint8_t* scratch, int* status, uint32_t* ctl,
                          hipStream_t stream);
+// The nested map's op path (map_map_apply.hip): R row i = S row i after its
+// ops of P in order; R's capacities >= S's, scratch of
+// map_map_apply_scratch_bytes(R, ..) bytes, 16-byte aligned (api.hip)
+size_t map_map_apply_scratch_bytes(const crdt_map_map_slab& R, uint64_t n_obj, uint32_t A);
+int launch_map_map_apply(const crdt_map_map_slab& S, const crdt_map_map_ops& P, const crdt_map_map_slab& R,
+                         uint64_t n_obj, uint32_t A, uint8_t* scratch, int* status, uint32_t* ctl,
+                         hipStream_t stream);
 int launch_map_orswot_merge(const crdt_map_orswot_slab& S, const crdt_map_orswot_slab& O,
                             const crdt_map_orswot_slab& R, uint64_t n_obj, uint32_t A, int* status, uint32_t* ctl,
                             hipStream_t stream, int variant = 0);

@@ -23,12 +23,14 @@
 // consecutive iterations are ordered by each lane's own program order; the
 // per-key / per-entry counts (mv_n, dset_n) are read and written by lane 0
 // only. keys[] and dset[] are searched by all lanes: every edit ends in
-// ma_sync(). The op headers, and the clock pairs of the first ops, are staged
+// ma_sync(). The per-op edits are map_mvreg_ws.h's (shared with the nested
+// map's op path, map_map_apply.hip, whose inner maps take them). The op headers, and the clock pairs of the first ops, are staged
 // in LDS 64 ops at a time, so that no op waits for its own header loads.
 #include <hip/hip_runtime.h>
 
 #include "../../include/crdts_hip.h"
 #include "kernels.h"
+#include "map_mvreg_ws.h"
 #include "map_rows.h"
 #include "sched.h"
 
@@ -36,65 +38,10 @@ namespace crdts_hip {
 namespace {
 
 using namespace maprow;
+using namespace mapws;
 
-constexpr uint32_t kMaW = 64;
-
-__device__ __forceinline__ void ma_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ uint32_t uni32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ uint64_t uni64(uint64_t v) {
-  return ((uint64_t)uni32((uint32_t)(v >> 32)) << 32) | (uint64_t)uni32((uint32_t)v);
-}
-// a count only lane 0 ever touches (mv_n / dset_n of the output row)
-__device__ __forceinline__ uint32_t cnt0(const uint32_t* p, uint32_t lane) {
-  uint32_t x = 0u;
-  if (lane == 0u) x = *p;
-  return uni32(x);
-}
-// n elements, lane l moving offsets l, l + 64, ... (the same lanes whatever the row)
-__device__ __forceinline__ void copy_n(uint64_t* dst, const uint64_t* src, uint32_t n, uint32_t lane) {
-  for (uint32_t e = lane; e < n; e += kMaW) dst[e] = src[e];
-}
-// a[k + 1] = a[k] for k in [p, n), the last 64 first; a[k - 1] = a[k] for k in
-// (p, n), the first 64 first: a chunk's loads are all done before its stores
-__device__ void shift_up(uint64_t* a, uint32_t p, uint32_t n, uint32_t lane) {
-  for (uint32_t hi = n; hi > p;) {
-    const uint32_t lo = hi - p > kMaW ? hi - kMaW : p;
-    const uint32_t k = lo + lane;
-    uint64_t x = 0ull;
-    if (k < hi) x = a[k];
-    ma_sync();
-    if (k < hi) a[k + 1u] = x;
-    ma_sync();
-    hi = lo;
-  }
-}
-__device__ void shift_down(uint64_t* a, uint32_t p, uint32_t n, uint32_t lane) {
-  for (uint32_t lo = p + 1u; lo < n; lo += kMaW) {
-    const uint32_t k = lo + lane;
-    uint64_t x = 0ull;
-    if (k < n) x = a[k];
-    ma_sync();
-    if (k < n) a[k - 1u] = x;
-    ma_sync();
-  }
-}
-// `key` in the ascending a[0, n): pos = how many are below it; is it there?
-__device__ bool find_key(const uint64_t* a, uint32_t n, uint64_t key, uint32_t lane, uint32_t& pos) {
-  uint32_t below = 0u;
-  bool hit = false;
-  for (uint32_t b = 0u; b < n; b += kMaW) {
-    const uint32_t k = b + lane;
-    const uint64_t x = k < n ? a[k] : ~0ull;
-    below += (uint32_t)__popcll(__ballot(k < n && x < key));
-    hit = hit || __ballot(k < n && x == key) != 0ull;
-  }
-  pos = below;
-  return hit;
-}
+constexpr uint32_t kMaW = kW;
+__device__ __forceinline__ void ma_sync() { mw_sync(); }
 
 // (7 waves/SIMD: bounded to 72 VGPRs, the kernel keeps a few values in
 // scratch and is faster than unbounded at 5 waves/SIMD — DESIGN.md §5h)
@@ -107,7 +54,7 @@ __global__ __launch_bounds__(kMaW, 7) void map_mvreg_apply_kernel(crdt_map_mvreg
   __shared__ uint32_t hkind[kMaW], hact[kMaW], pact[kMaW];
   __shared__ uint64_t hkey[kMaW], hctr[kMaW], hval[kMaW], hend[kMaW], pctr[kMaW];
   const uint32_t lane = threadIdx.x;
-  const uint64_t Rk = R.kcap, Rm = R.mcap, Rd = R.dcap, Rs = R.scap;
+  const uint64_t Rm = R.mcap, Rs = R.scap;
   BlockTickets<4> sched(n_obj, ctl + 3, lane);
   for (uint64_t i = sched.first(); i < n_obj; i = sched.next(i)) {
     // ---- the input row, checked as the merge checks it (map.hip)
@@ -127,22 +74,23 @@ __global__ __launch_bounds__(kMaW, 7) void map_mvreg_apply_kernel(crdt_map_mvreg
       continue;
     }
     // ---- out[i]'s arrays; self[i]'s used slots copied in (out caps >= self's: api.hip)
-    uint64_t* const keys = R.keys + i * Rk;
-    uint64_t* const ecl = R.eclock + i * Rk * A;
-    uint32_t* const mvn = R.mv_n + i * Rk;
-    uint64_t* const mvc = R.mv_clock + i * Rk * Rm * A;
-    uint64_t* const mvv = R.mv_val + i * Rk * Rm;
-    uint64_t* const dcl = R.dclock + i * Rd * A;
-    uint32_t* const dsn = R.dset_n + i * Rd;
-    uint64_t* const dse = R.dset + i * Rd * Rs;
+    const MapRef m = map_ref(R, i, A);
+    uint64_t* const keys = m.keys;
+    uint64_t* const ecl = m.ecl;
+    uint32_t* const mvn = m.mvn;
+    uint64_t* const mvc = m.mvc;
+    uint64_t* const mvv = m.mvv;
+    uint64_t* const dcl = m.def.dcl;
+    uint32_t* const dsn = m.def.dsn;
+    uint64_t* const dse = m.def.dse;
     copy_n(keys, S.keys + i * S.kcap, nS, lane);
     copy_n(ecl, S.eclock + i * S.kcap * A, nS * A, lane);
     for (uint32_t k = 0; k < nS; ++k) {
       const uint64_t sk = i * S.kcap + k;
-      const uint32_t m = k < kMaW ? (uint32_t)__builtin_amdgcn_readlane(vnS, k) : uni32(S.mv_n[sk]);
-      if (lane == 0u) mvn[k] = m;
-      copy_n(mvc + k * Rm * A, S.mv_clock + sk * S.mcap * A, m * A, lane);
-      copy_n(mvv + k * Rm, S.mv_val + sk * S.mcap, m, lane);
+      const uint32_t vn = k < kMaW ? (uint32_t)__builtin_amdgcn_readlane(vnS, k) : uni32(S.mv_n[sk]);
+      if (lane == 0u) mvn[k] = vn;
+      copy_n(mvc + k * Rm * A, S.mv_clock + sk * S.mcap * A, vn * A, lane);
+      copy_n(mvv + k * Rm, S.mv_val + sk * S.mcap, vn, lane);
     }
     copy_n(dcl, S.dclock + i * S.dcap * A, dS * A, lane);
     for (uint32_t d = 0; d < dS; ++d) {
@@ -151,44 +99,12 @@ __global__ __launch_bounds__(kMaW, 7) void map_mvreg_apply_kernel(crdt_map_mvreg
       if (lane == 0u) dsn[d] = sn;
       copy_n(dse + d * Rs, S.dset + sd * S.scap, sn, lane);
     }
-    Row<NS> cM = rowv<NS>(S.clock, i, A, lane);  // the map clock, in registers across the op list
-    uint32_t nk = nS, nd = dS;
+    MapSt<NS> st;  // the map clock and the two counts, in registers across the op list
+    st.cM = rowv<NS>(S.clock, i, A, lane);
+    st.nk = nS;
+    st.nd = dS;
     int err = 0;
     ma_sync();
-
-    // apply_rm's entry edit (src/map.rs:341-349): the key's entry clock loses
-    // D; an emptied entry is removed, else its register is truncated by D
-    auto rm_entry = [&](uint64_t key, const Row<NS>& D) {
-      uint32_t pos;
-      if (!find_key(keys, nk, key, lane, pos)) return;
-      const Row<NS> ec = vsub(ldrow<NS>(ecl + (uint64_t)pos * A, A, lane), D);
-      if (!vany(ec)) {
-        for (uint32_t k = pos + 1u; k < nk; ++k) {  // rows above it one slot down, first row first
-          const uint32_t m = cnt0(mvn + k, lane);
-          strow<NS>(ecl + (uint64_t)(k - 1u) * A, ldrow<NS>(ecl + (uint64_t)k * A, A, lane), A, lane);
-          copy_n(mvc + (k - 1u) * Rm * A, mvc + k * Rm * A, m * A, lane);
-          copy_n(mvv + (k - 1u) * Rm, mvv + k * Rm, m, lane);
-          if (lane == 0u) mvn[k - 1u] = m;
-        }
-        shift_down(keys, pos, nk, lane);
-        --nk;
-      } else {
-        strow<NS>(ecl + (uint64_t)pos * A, ec, A, lane);
-        const uint32_t m = cnt0(mvn + pos, lane);
-        uint64_t* const vc = mvc + pos * Rm * A;
-        uint64_t* const vv = mvv + pos * Rm;
-        uint32_t w = 0;
-        for (uint32_t v = 0; v < m; ++v) {  // MVReg::truncate, order kept
-          const Row<NS> r = vsub(ldrow<NS>(vc + (uint64_t)v * A, A, lane), D);
-          if (!vany(r)) continue;
-          strow<NS>(vc + (uint64_t)w * A, r, A, lane);
-          if (lane == 0u && w != v) vv[w] = vv[v];
-          ++w;
-        }
-        if (lane == 0u) mvn[pos] = w;
-      }
-      ma_sync();
-    };
 
     // The op headers are staged in LDS 64 ops at a time (slot t: the chunk's op
     // t), with the first 64 clock pairs of those ops, before the chunk's edits
@@ -257,150 +173,26 @@ __global__ __launch_bounds__(kMaW, 7) void map_mvreg_apply_kernel(crdt_map_mvreg
       const Row<NS> C = ldrow<NS>(oc, A, lane);
 
       if (kind == CRDT_MAP_OP_RM) {
-        if (!vany(C)) continue;  // empty <= every clock, and subtracts nothing
-        if (!vle(C, cM)) {       // deferred: into an equal clock's key set, or a new entry in CLOCK ORDER
-          uint32_t at = nd;
-          bool eq = false;
-          for (uint32_t d = 0; d < nd; ++d) {
-            const int o = vorder(C, ldrow<NS>(dcl + (uint64_t)d * A, A, lane), lane);
-            if (o > 0) continue;
-            at = d;
-            eq = o == 0;
-            break;
-          }
-          if (eq) {
-            uint64_t* const set = dse + at * Rs;
-            const uint32_t sn = cnt0(dsn + at, lane);
-            uint32_t p;
-            if (!find_key(set, sn, key, lane, p)) {
-              if (sn >= R.scap) {
-                err = CRDT_ECAPACITY;
-                break;
-              }
-              shift_up(set, p, sn, lane);
-              if (lane == 0u) {
-                set[p] = key;
-                dsn[at] = sn + 1u;
-              }
-            }
-          } else {
-            if (nd >= R.dcap) {
-              err = CRDT_ECAPACITY;
-              break;
-            }
-            for (uint32_t d = nd; d-- > at;) {  // entries from `at` one slot up, last first
-              const uint32_t sn = cnt0(dsn + d, lane);
-              strow<NS>(dcl + (uint64_t)(d + 1u) * A, ldrow<NS>(dcl + (uint64_t)d * A, A, lane), A, lane);
-              copy_n(dse + (d + 1u) * Rs, dse + d * Rs, sn, lane);
-              if (lane == 0u) dsn[d + 1u] = sn;
-            }
-            // lane 0 writes the new set's only element: offset 0 is lane 0's in copy_n
-            strow<NS>(dcl + (uint64_t)at * A, C, A, lane);
-            if (lane == 0u) {
-              dse[at * Rs] = key;
-              dsn[at] = 1u;
-            }
-            ++nd;
-          }
-          ma_sync();
-        }
-        rm_entry(key, C);
+        err = map_rm<NS>(m, st, key, C, A, lane);
         continue;
       }
-
       // ---- Op::Up
       const uint32_t da = uni32(hact[t]);
-      const uint64_t dc = uni64(hctr[t]);
       if (da >= A) {
         err = CRDT_ENONCANON;
         break;
       }
-      const uint32_t ds = da >> 6, dl = da & 63u;
-      uint64_t seen = 0ull;
-      for (int s = 0; s < NS; ++s)
-        if ((uint32_t)s == ds) seen = lane64(cM.v[s], dl);
-      if (seen >= dc) continue;  // the map has this dot: the whole op is skipped
-      uint32_t pos;
-      const bool found = find_key(keys, nk, key, lane, pos);
-      if (!found) {
-        if (nk >= R.kcap) {
-          err = CRDT_ECAPACITY;
-          break;
-        }
-        for (uint32_t k = nk; k-- > pos;) {  // rows from pos one slot up, last row first
-          const uint32_t m = cnt0(mvn + k, lane);
-          strow<NS>(ecl + (uint64_t)(k + 1u) * A, ldrow<NS>(ecl + (uint64_t)k * A, A, lane), A, lane);
-          copy_n(mvc + (k + 1u) * Rm * A, mvc + k * Rm * A, m * A, lane);
-          copy_n(mvv + (k + 1u) * Rm, mvv + k * Rm, m, lane);
-          if (lane == 0u) mvn[k + 1u] = m;
-        }
-        shift_up(keys, pos, nk, lane);
-        if (lane == 0u) keys[pos] = key;
-        ++nk;
-      }
-      Row<NS> ec = found ? ldrow<NS>(ecl + (uint64_t)pos * A, A, lane) : zrow<NS>();
-      for (int s = 0; s < NS; ++s) {  // witness(dot) on the entry clock and on the map clock
-        if ((uint32_t)s != ds || lane != dl) continue;
-        ec.v[s] = ec.v[s] > dc ? ec.v[s] : dc;
-        cM.v[s] = dc;
-      }
-      strow<NS>(ecl + (uint64_t)pos * A, ec, A, lane);
-      uint32_t m = found ? cnt0(mvn + pos, lane) : 0u;
-      if (vany(C)) {  // MVReg Put: drop the values the clock covers, append unless one is ahead
-        uint64_t* const vc = mvc + pos * Rm * A;
-        uint64_t* const vv = mvv + pos * Rm;
-        uint32_t w = 0;
-        bool ahead = false;
-        for (uint32_t v = 0; v < m; ++v) {
-          const Row<NS> r = ldrow<NS>(vc + (uint64_t)v * A, A, lane);
-          if (vle(r, C)) continue;
-          ahead = ahead || vstrict_less(C, r);
-          if (w != v) {
-            strow<NS>(vc + (uint64_t)w * A, r, A, lane);
-            if (lane == 0u) vv[w] = vv[v];
-          }
-          ++w;
-        }
-        if (!ahead) {
-          if (w >= R.mcap) {
-            err = CRDT_ECAPACITY;
-            break;
-          }
-          strow<NS>(vc + (uint64_t)w * A, C, A, lane);
-          if (lane == 0u) vv[w] = hval[t];
-          ++w;
-        }
-        m = w;
-      }
-      if (lane == 0u) mvn[pos] = m;
-      ma_sync();
-      // ---- apply_deferred: every (clock, key) removed again; the clocks the
-      // map clock still does not cover stay, with their sets
-      uint32_t w = 0;
-      for (uint32_t d = 0; d < nd; ++d) {
-        const Row<NS> D = ldrow<NS>(dcl + (uint64_t)d * A, A, lane);
-        const uint32_t sn = cnt0(dsn + d, lane);
-        for (uint32_t s = 0; s < sn; ++s) rm_entry(uni64(dse[d * Rs + s]), D);
-        if (vle(D, cM)) continue;
-        if (w != d) {
-          strow<NS>(dcl + (uint64_t)w * A, D, A, lane);
-          copy_n(dse + w * Rs, dse + d * Rs, sn, lane);
-          if (lane == 0u) dsn[w] = sn;
-        }
-        ++w;
-      }
-      if (w != nd) ma_sync();
-      nd = w;
+      err = map_up<NS>(m, st, da, uni64(hctr[t]), key, C, uni64(hval[t]), A, lane);
     }
     if (err) {
       if (lane == 0u) atomicCAS(status, 0, err);
       continue;
     }
     if (lane == 0u) {
-      R.n_keys[i] = nk;
-      R.n_def[i] = nd;
+      R.n_keys[i] = st.nk;
+      R.n_def[i] = st.nd;
     }
-    strow<NS>(R.clock + i * A, cM, A, lane);
+    strow<NS>(R.clock + i * A, st.cM, A, lane);
   }
 }
 

@@ -1,0 +1,455 @@
+// One Map<u64, MVReg<u64, A>, A> row edited in place by one wave (internal):
+// the per-op edits of Map::apply (src/map.rs:160-190) and Map::truncate
+// (:131-158) as device functions over (slab, row), for the kernels that hold
+// such a map as a value — the nested map's op path (map_map_apply.hip), whose
+// inner maps are rows of a scratch slab.
+//
+// Lane = actor slot (map_rows.h). A row's arrays are touched under fixed lane
+// mappings: a clock row by the lane of its actor slot (ldrow / strow); a
+// block of elements by lane e % 64 (copy_n); the per-key / per-entry counts
+// (mv_n, dset_n) and single values by lane 0. An address is used under one
+// mapping between two mw_sync() and every edit ends in one, so a lane's own
+// program order covers the rest. keys[] and dset[] are searched by all lanes.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/crdts_hip.h"
+#include "map_rows.h"
+
+namespace crdts_hip {
+namespace mapws {
+
+using namespace maprow;
+
+constexpr uint32_t kW = 64;
+
+__device__ __forceinline__ void mw_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ uint32_t uni32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ uint64_t uni64(uint64_t v) {
+  return ((uint64_t)uni32((uint32_t)(v >> 32)) << 32) | (uint64_t)uni32((uint32_t)v);
+}
+// a value only lane 0 ever touches
+__device__ __forceinline__ uint32_t cnt0(const uint32_t* p, uint32_t lane) {
+  uint32_t x = 0u;
+  if (lane == 0u) x = *p;
+  return uni32(x);
+}
+__device__ __forceinline__ uint64_t val0(const uint64_t* p, uint32_t lane) {
+  uint64_t x = 0ull;
+  if (lane == 0u) x = *p;
+  return uni64(x);
+}
+// n elements, lane l moving offsets l, l + 64, ...
+__device__ __forceinline__ void copy_n(uint64_t* dst, const uint64_t* src, uint32_t n, uint32_t lane) {
+  for (uint32_t e = lane; e < n; e += kW) dst[e] = src[e];
+}
+// a[k + 1] = a[k] for k in [p, n), the last 64 first; a[k - 1] = a[k] for k in
+// (p, n), the first 64 first: a chunk's loads are all done before its stores
+__device__ inline void shift_up(uint64_t* a, uint32_t p, uint32_t n, uint32_t lane) {
+  for (uint32_t hi = n; hi > p;) {
+    const uint32_t lo = hi - p > kW ? hi - kW : p;
+    const uint32_t k = lo + lane;
+    uint64_t x = 0ull;
+    if (k < hi) x = a[k];
+    mw_sync();
+    if (k < hi) a[k + 1u] = x;
+    mw_sync();
+    hi = lo;
+  }
+}
+__device__ inline void shift_down(uint64_t* a, uint32_t p, uint32_t n, uint32_t lane) {
+  for (uint32_t lo = p + 1u; lo < n; lo += kW) {
+    const uint32_t k = lo + lane;
+    uint64_t x = 0ull;
+    if (k < n) x = a[k];
+    mw_sync();
+    if (k < n) a[k - 1u] = x;
+    mw_sync();
+  }
+}
+// `key` in the ascending a[0, n): pos = how many are below it; is it there?
+__device__ inline bool find_key(const uint64_t* a, uint32_t n, uint64_t key, uint32_t lane, uint32_t& pos) {
+  uint32_t below = 0u;
+  bool hit = false;
+  for (uint32_t b = 0u; b < n; b += kW) {
+    const uint32_t k = b + lane;
+    const uint64_t x = k < n ? a[k] : ~0ull;
+    below += (uint32_t)__popcll(__ballot(k < n && x < key));
+    hit = hit || __ballot(k < n && x == key) != 0ull;
+  }
+  pos = below;
+  return hit;
+}
+
+// ---- the deferred removes of one map: clocks [Rd][A] in CLOCK ORDER, their
+// key sets [Rd][Rs] ascending (an outer map's or an inner map's alike)
+struct DefRef {
+  uint64_t* dcl;
+  uint32_t* dsn;
+  uint64_t* dse;
+  uint32_t Rd, Rs;
+};
+// entry src -> slot dst (dst != src)
+template <int NS>
+__device__ inline void def_move(const DefRef& d, uint32_t dst, uint32_t src, uint32_t A, uint32_t lane) {
+  const uint32_t sn = cnt0(d.dsn + src, lane);
+  strow<NS>(d.dcl + (uint64_t)dst * A, ldrow<NS>(d.dcl + (uint64_t)src * A, A, lane), A, lane);
+  copy_n(d.dse + (uint64_t)dst * d.Rs, d.dse + (uint64_t)src * d.Rs, sn, lane);
+  if (lane == 0u) d.dsn[dst] = sn;
+}
+template <int NS>
+__device__ inline void def_swap(const DefRef& d, uint32_t p, uint32_t q, uint32_t A, uint32_t lane) {
+  const uint32_t np = cnt0(d.dsn + p, lane), nq = cnt0(d.dsn + q, lane);
+  const Row<NS> rp = ldrow<NS>(d.dcl + (uint64_t)p * A, A, lane), rq = ldrow<NS>(d.dcl + (uint64_t)q * A, A, lane);
+  strow<NS>(d.dcl + (uint64_t)p * A, rq, A, lane);
+  strow<NS>(d.dcl + (uint64_t)q * A, rp, A, lane);
+  uint64_t* const sp = d.dse + (uint64_t)p * d.Rs;
+  uint64_t* const sq = d.dse + (uint64_t)q * d.Rs;
+  for (uint32_t e = lane; e < (np > nq ? np : nq); e += kW) {  // both counts <= Rs
+    const uint64_t x = sp[e], y = sq[e];
+    sp[e] = y;
+    sq[e] = x;
+  }
+  if (lane == 0u) {
+    d.dsn[p] = nq;
+    d.dsn[q] = np;
+  }
+}
+// apply_rm's deferral (src/map.rs:337-341) of a clock the map clock does not
+// cover: the key joins an equal clock's set, or a new entry is inserted at its
+// CLOCK ORDER place. 0, or CRDT_ECAPACITY.
+template <int NS>
+__device__ inline int def_insert(const DefRef& d, uint32_t& nd, uint64_t key, const Row<NS>& C, uint32_t A,
+                                 uint32_t lane) {
+  uint32_t at = nd;
+  bool eq = false;
+  for (uint32_t e = 0; e < nd; ++e) {
+    const int o = vorder(C, ldrow<NS>(d.dcl + (uint64_t)e * A, A, lane), lane);
+    if (o > 0) continue;
+    at = e;
+    eq = o == 0;
+    break;
+  }
+  if (eq) {
+    uint64_t* const set = d.dse + (uint64_t)at * d.Rs;
+    const uint32_t sn = cnt0(d.dsn + at, lane);
+    uint32_t p;
+    if (!find_key(set, sn, key, lane, p)) {
+      if (sn >= d.Rs) return CRDT_ECAPACITY;
+      shift_up(set, p, sn, lane);
+      if (lane == 0u) {
+        set[p] = key;
+        d.dsn[at] = sn + 1u;
+      }
+    }
+  } else {
+    if (nd >= d.Rd) return CRDT_ECAPACITY;
+    for (uint32_t e = nd; e-- > at;) def_move<NS>(d, e + 1u, e, A, lane);  // entries from `at` one slot up, last first
+    // lane 0 writes the new set's only element: offset 0 is lane 0's in copy_n
+    strow<NS>(d.dcl + (uint64_t)at * A, C, A, lane);
+    if (lane == 0u) {
+      d.dse[(uint64_t)at * d.Rs] = key;
+      d.dsn[at] = 1u;
+    }
+    ++nd;
+  }
+  mw_sync();
+  return 0;
+}
+
+// ---- one Map<u64, MVReg> row of a slab, and its state held in registers
+struct MapRef {
+  uint64_t* clock;
+  uint32_t* n_keys;
+  uint32_t* n_def;
+  uint64_t* keys;
+  uint64_t* ecl;
+  uint32_t* mvn;
+  uint64_t* mvc;
+  uint64_t* mvv;
+  DefRef def;
+  uint32_t Rk, Rm;
+};
+template <int NS>
+struct MapSt {
+  Row<NS> cM;
+  uint32_t nk, nd;
+};
+__device__ __forceinline__ MapRef map_ref(const crdt_map_mvreg_slab& R, uint64_t row, uint32_t A) {
+  MapRef m;
+  m.clock = R.clock + row * A;
+  m.n_keys = R.n_keys + row;
+  m.n_def = R.n_def + row;
+  m.keys = R.keys + row * R.kcap;
+  m.ecl = R.eclock + row * R.kcap * A;
+  m.mvn = R.mv_n + row * R.kcap;
+  m.mvc = R.mv_clock + row * R.kcap * R.mcap * A;
+  m.mvv = R.mv_val + row * R.kcap * R.mcap;
+  m.def.dcl = R.dclock + row * R.dcap * A;
+  m.def.dsn = R.dset_n + row * R.dcap;
+  m.def.dse = R.dset + row * R.dcap * R.scap;
+  m.def.Rd = R.dcap;
+  m.def.Rs = R.scap;
+  m.Rk = R.kcap;
+  m.Rm = R.mcap;
+  return m;
+}
+template <int NS>
+__device__ inline MapSt<NS> map_open(const MapRef& m, uint32_t A, uint32_t lane) {
+  MapSt<NS> st;
+  st.cM = ldrow<NS>(m.clock, A, lane);
+  st.nk = cnt0(m.n_keys, lane);
+  st.nd = cnt0(m.n_def, lane);
+  return st;
+}
+template <int NS>
+__device__ inline void map_close(const MapRef& m, const MapSt<NS>& st, uint32_t A, uint32_t lane) {
+  strow<NS>(m.clock, st.cM, A, lane);
+  if (lane == 0u) {
+    *m.n_keys = st.nk;
+    *m.n_def = st.nd;
+  }
+  mw_sync();
+}
+// an empty map in row `m`
+template <int NS>
+__device__ inline void map_clear(const MapRef& m, uint32_t A, uint32_t lane) {
+  MapSt<NS> st;
+  st.cM = zrow<NS>();
+  st.nk = st.nd = 0u;
+  map_close<NS>(m, st, A, lane);
+}
+
+// Row srow of S -> row rrow of R, used slots only (R's capacities >= S's).
+// false, and nothing written, for a row the merge rejects (a count above its
+// capacity). Ends in mw_sync().
+__device__ inline bool map_copy_row(const crdt_map_mvreg_slab& S, uint64_t srow, const crdt_map_mvreg_slab& R,
+                                    uint64_t rrow, uint32_t A, uint32_t lane) {
+  const uint32_t nS = uni32(S.n_keys[srow]), dS = uni32(S.n_def[srow]);
+  if (nS > S.kcap || dS > S.dcap) return false;
+  const uint32_t vnS = lane < nS ? S.mv_n[srow * S.kcap + lane] : 0u;
+  const uint32_t dnS = lane < dS ? S.dset_n[srow * S.dcap + lane] : 0u;
+  bool bad = vnS > S.mcap || dnS > S.scap;
+  for (uint32_t k = lane + kW; k < nS; k += kW) bad = bad || S.mv_n[srow * S.kcap + k] > S.mcap;
+  for (uint32_t d = lane + kW; d < dS; d += kW) bad = bad || S.dset_n[srow * S.dcap + d] > S.scap;
+  if (__ballot(bad) != 0ull) return false;
+  const MapRef m = map_ref(R, rrow, A);
+  copy_n(m.clock, S.clock + srow * A, A, lane);
+  copy_n(m.keys, S.keys + srow * S.kcap, nS, lane);
+  copy_n(m.ecl, S.eclock + srow * S.kcap * A, nS * A, lane);
+  for (uint32_t k = 0; k < nS; ++k) {
+    const uint64_t sk = srow * S.kcap + k;
+    const uint32_t n = k < kW ? (uint32_t)__builtin_amdgcn_readlane(vnS, k) : uni32(S.mv_n[sk]);
+    if (lane == 0u) m.mvn[k] = n;
+    copy_n(m.mvc + (uint64_t)k * m.Rm * A, S.mv_clock + sk * S.mcap * A, n * A, lane);
+    copy_n(m.mvv + (uint64_t)k * m.Rm, S.mv_val + sk * S.mcap, n, lane);
+  }
+  copy_n(m.def.dcl, S.dclock + srow * S.dcap * A, dS * A, lane);
+  for (uint32_t d = 0; d < dS; ++d) {
+    const uint64_t sd = srow * S.dcap + d;
+    const uint32_t sn = d < kW ? (uint32_t)__builtin_amdgcn_readlane(dnS, d) : uni32(S.dset_n[sd]);
+    if (lane == 0u) m.def.dsn[d] = sn;
+    copy_n(m.def.dse + (uint64_t)d * m.def.Rs, S.dset + sd * S.scap, sn, lane);
+  }
+  if (lane == 0u) {
+    *m.n_keys = nS;
+    *m.n_def = dS;
+  }
+  mw_sync();
+  return true;
+}
+
+// apply_rm's entry edit (src/map.rs:343-349): the key's entry clock loses D;
+// an emptied entry is removed, else its register takes MVReg::truncate(D)
+// (src/mvreg.rs:100-113, order kept)
+template <int NS>
+__device__ inline void map_rm_entry(const MapRef& m, MapSt<NS>& st, uint64_t key, const Row<NS>& D, uint32_t A,
+                                    uint32_t lane) {
+  const uint64_t Rm = m.Rm;
+  uint32_t pos;
+  if (!find_key(m.keys, st.nk, key, lane, pos)) return;
+  const Row<NS> ec = vsub(ldrow<NS>(m.ecl + (uint64_t)pos * A, A, lane), D);
+  if (!vany(ec)) {
+    for (uint32_t k = pos + 1u; k < st.nk; ++k) {  // rows above it one slot down, first row first
+      const uint32_t n = cnt0(m.mvn + k, lane);
+      strow<NS>(m.ecl + (uint64_t)(k - 1u) * A, ldrow<NS>(m.ecl + (uint64_t)k * A, A, lane), A, lane);
+      copy_n(m.mvc + (k - 1u) * Rm * A, m.mvc + k * Rm * A, n * A, lane);
+      copy_n(m.mvv + (k - 1u) * Rm, m.mvv + k * Rm, n, lane);
+      if (lane == 0u) m.mvn[k - 1u] = n;
+    }
+    shift_down(m.keys, pos, st.nk, lane);
+    --st.nk;
+  } else {
+    strow<NS>(m.ecl + (uint64_t)pos * A, ec, A, lane);
+    const uint32_t n = cnt0(m.mvn + pos, lane);
+    uint64_t* const vc = m.mvc + pos * Rm * A;
+    uint64_t* const vv = m.mvv + pos * Rm;
+    uint32_t w = 0;
+    for (uint32_t v = 0; v < n; ++v) {
+      const Row<NS> r = vsub(ldrow<NS>(vc + (uint64_t)v * A, A, lane), D);
+      if (!vany(r)) continue;
+      strow<NS>(vc + (uint64_t)w * A, r, A, lane);
+      if (lane == 0u && w != v) vv[w] = vv[v];
+      ++w;
+    }
+    if (lane == 0u) m.mvn[pos] = w;
+  }
+  mw_sync();
+}
+
+// Op::Rm -> apply_rm (src/map.rs:336-350). 0, or CRDT_ECAPACITY.
+template <int NS>
+__device__ inline int map_rm(const MapRef& m, MapSt<NS>& st, uint64_t key, const Row<NS>& C, uint32_t A,
+                             uint32_t lane) {
+  if (!vany(C)) return 0;  // empty <= every clock, and subtracts nothing
+  if (!vle(C, st.cM)) {
+    const int e = def_insert<NS>(m.def, st.nd, key, C, A, lane);
+    if (e) return e;
+  }
+  map_rm_entry<NS>(m, st, key, C, A, lane);
+  return 0;
+}
+
+// Op::Up { dot (da, dc), key, Put { C, val } } (src/map.rs:169-187, the Put:
+// src/mvreg.rs:158-186), da < A. 0, or CRDT_ECAPACITY.
+template <int NS>
+__device__ inline int map_up(const MapRef& m, MapSt<NS>& st, uint32_t da, uint64_t dc, uint64_t key,
+                             const Row<NS>& C, uint64_t val, uint32_t A, uint32_t lane) {
+  const uint64_t Rm = m.Rm;
+  const uint32_t ds = da >> 6, dl = da & 63u;
+  uint64_t seen = 0ull;
+  for (int s = 0; s < NS; ++s)
+    if ((uint32_t)s == ds) seen = lane64(st.cM.v[s], dl);
+  if (seen >= dc) return 0;  // the map has this dot: the whole op is skipped
+  uint32_t pos;
+  const bool found = find_key(m.keys, st.nk, key, lane, pos);
+  if (!found) {
+    if (st.nk >= m.Rk) return CRDT_ECAPACITY;
+    for (uint32_t k = st.nk; k-- > pos;) {  // rows from pos one slot up, last row first
+      const uint32_t n = cnt0(m.mvn + k, lane);
+      strow<NS>(m.ecl + (uint64_t)(k + 1u) * A, ldrow<NS>(m.ecl + (uint64_t)k * A, A, lane), A, lane);
+      copy_n(m.mvc + (k + 1u) * Rm * A, m.mvc + k * Rm * A, n * A, lane);
+      copy_n(m.mvv + (k + 1u) * Rm, m.mvv + k * Rm, n, lane);
+      if (lane == 0u) m.mvn[k + 1u] = n;
+    }
+    shift_up(m.keys, pos, st.nk, lane);
+    if (lane == 0u) m.keys[pos] = key;
+    ++st.nk;
+  }
+  Row<NS> ec = found ? ldrow<NS>(m.ecl + (uint64_t)pos * A, A, lane) : zrow<NS>();
+  for (int s = 0; s < NS; ++s) {  // witness(dot) on the entry clock and on the map clock
+    if ((uint32_t)s != ds || lane != dl) continue;
+    ec.v[s] = ec.v[s] > dc ? ec.v[s] : dc;
+    st.cM.v[s] = dc;
+  }
+  strow<NS>(m.ecl + (uint64_t)pos * A, ec, A, lane);
+  uint32_t n = found ? cnt0(m.mvn + pos, lane) : 0u;
+  if (vany(C)) {  // MVReg Put: drop the values the clock covers, append unless one is ahead
+    uint64_t* const vc = m.mvc + pos * Rm * A;
+    uint64_t* const vv = m.mvv + pos * Rm;
+    uint32_t w = 0;
+    bool ahead = false;
+    for (uint32_t v = 0; v < n; ++v) {
+      const Row<NS> r = ldrow<NS>(vc + (uint64_t)v * A, A, lane);
+      if (vle(r, C)) continue;
+      ahead = ahead || vstrict_less(C, r);
+      if (w != v) {
+        strow<NS>(vc + (uint64_t)w * A, r, A, lane);
+        if (lane == 0u) vv[w] = vv[v];
+      }
+      ++w;
+    }
+    if (!ahead) {
+      if (w >= m.Rm) return CRDT_ECAPACITY;
+      strow<NS>(vc + (uint64_t)w * A, C, A, lane);
+      if (lane == 0u) vv[w] = val;
+      ++w;
+    }
+    n = w;
+  }
+  if (lane == 0u) m.mvn[pos] = n;
+  mw_sync();
+  // apply_deferred (:325-333): every (clock, key) removed again; the clocks
+  // the map clock still does not cover stay, with their sets (a subsequence
+  // of a CLOCK ORDER list is in CLOCK ORDER)
+  const DefRef& d = m.def;
+  uint32_t w = 0;
+  for (uint32_t e = 0; e < st.nd; ++e) {
+    const Row<NS> D = ldrow<NS>(d.dcl + (uint64_t)e * A, A, lane);
+    const uint32_t sn = cnt0(d.dsn + e, lane);
+    for (uint32_t s = 0; s < sn; ++s) map_rm_entry<NS>(m, st, uni64(d.dse[(uint64_t)e * d.Rs + s]), D, A, lane);
+    if (vle(D, st.cM)) continue;
+    if (w != e) def_move<NS>(d, w, e, A, lane);
+    ++w;
+  }
+  if (w != st.nd) mw_sync();
+  st.nd = w;
+  return 0;
+}
+
+// Map::truncate(T) (src/map.rs:131-158): every entry clock loses T, an emptied
+// entry is dropped, any other takes MVReg::truncate(T); every deferred clock
+// loses T, an emptied one is dropped, the rest go back in CLOCK ORDER — where
+// two become equal, the key set of the later one (CLOCK ORDER before the
+// subtract) is kept, as crdt_map_map_merge does; the map clock loses T.
+template <int NS>
+__device__ inline void map_truncate(const MapRef& m, MapSt<NS>& st, const Row<NS>& T, uint32_t A, uint32_t lane) {
+  const uint64_t Rm = m.Rm;
+  uint32_t w = 0;
+  for (uint32_t k = 0; k < st.nk; ++k) {  // entries compacted forwards: slot w <= k
+    const Row<NS> ec = vsub(ldrow<NS>(m.ecl + (uint64_t)k * A, A, lane), T);
+    if (!vany(ec)) continue;
+    strow<NS>(m.ecl + (uint64_t)w * A, ec, A, lane);
+    const uint32_t n = cnt0(m.mvn + k, lane);
+    uint32_t wv = 0;
+    for (uint32_t v = 0; v < n; ++v) {
+      const Row<NS> r = vsub(ldrow<NS>(m.mvc + (k * Rm + v) * A, A, lane), T);
+      if (!vany(r)) continue;
+      strow<NS>(m.mvc + (w * Rm + wv) * A, r, A, lane);
+      if (lane == 0u) m.mvv[w * Rm + wv] = m.mvv[k * Rm + v];
+      ++wv;
+    }
+    if (lane == 0u) {
+      m.mvn[w] = wv;
+      if (w != k) m.keys[w] = m.keys[k];
+    }
+    ++w;
+  }
+  st.nk = w;
+  const DefRef& d = m.def;
+  uint32_t wd = 0;
+  for (uint32_t e = 0; e < st.nd; ++e) {
+    const Row<NS> D = vsub(ldrow<NS>(d.dcl + (uint64_t)e * A, A, lane), T);
+    if (!vany(D)) continue;
+    if (wd != e) def_move<NS>(d, wd, e, A, lane);
+    strow<NS>(d.dcl + (uint64_t)wd * A, D, A, lane);
+    // from slot wd down to its CLOCK ORDER place among the kept ones
+    uint32_t p = wd;
+    bool dup = false;
+    while (p > 0u) {
+      const int o = vorder(D, ldrow<NS>(d.dcl + (uint64_t)(p - 1u) * A, A, lane), lane);
+      if (o > 0) break;
+      if (o == 0) {
+        dup = true;
+        break;
+      }
+      def_swap<NS>(d, p, p - 1u, A, lane);
+      --p;
+    }
+    if (dup) {  // its set replaces the equal clock's; the entries it passed go one slot down
+      for (uint32_t q = p; q <= wd; ++q) def_move<NS>(d, q - 1u, q, A, lane);
+    } else {
+      ++wd;
+    }
+  }
+  st.nd = wd;
+  st.cM = vsub(st.cM, T);
+  mw_sync();
+}
+
+}  // namespace mapws
+}  // namespace crdts_hip
