@@ -887,6 +887,71 @@ int crdt_mvreg_merge(crdt_ctx* ctx, const uint32_t* d_self_n, const uint64_t* d_
                      size_t n_obj, uint32_t n_actors, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * MVReg<u64, A> op path, batched, over crdt_mvreg_merge's slabs (n[i] slots
+ * in use, clk[i][cap][n_actors] dense rows with 0 = absent, val[i][cap], Vec
+ * order). Outputs follow the merge's convention: survivors in order, every
+ * unused slot of d_out_clk / d_out_val zero-filled. Not in place.
+ *
+ * crdt_mvreg_apply: out[i] = self[i] after object i's Op::Put list in order
+ * (CmRDT::apply, src/mvreg.rs:158-186). The op batch is crdt_map_mvreg_ops
+ * without the map fields: object i owns ops [obj_end[i-1], obj_end[i]), op j
+ * the clock pairs [clk_end[j-1], clk_end[j]) of clk_act / clk_ctr (actors
+ * strictly increasing and < n_actors, counters > 0).
+ *   - a Put with an empty clock (no pairs) leaves the register unchanged
+ *     (:161-163);
+ *   - any other Put first drops every value whose clock is <= the Put clock
+ *     pointwise, equal clocks included (:165), order kept; then appends
+ *     (clock, val) unless a remaining clock is strictly greater (:173-183).
+ *     A Put may drop a value and still not be added.
+ *   Input rows are taken as given: an all-zero stored row is <= every
+ *   non-empty Put clock and is dropped by it.
+ * crdt_mvreg_truncate: Causal::truncate (src/mvreg.rs:100-113) of register i
+ * by d_clock[i] (dense [n_obj][n_actors], 0 = absent): every row loses each
+ * actor whose counter is <= the truncating clock's (VClock::subtract,
+ * src/vclock.rs:236-242); a slot whose row becomes all zero is dropped, order
+ * kept. An all-zero truncating row is the identity.
+ * crdt_mvreg_read_clock: d_out_clock[i] = read().add_clock (src/mvreg.rs:
+ * 201-222), the pointwise max over the n[i] used rows (all zero for an empty
+ * register); slots past n[i] are not read.
+ *
+ * CRDT_EINVAL (before any device work): a null ctx; a null ops struct
+ * (crdt_mvreg_apply; also with n_obj == 0: the struct is always read); a
+ * null array with n_obj > 0; n_actors == 0; self_cap == 0 or > 1024; out_cap
+ * < self_cap or > 2048 (crdt_mvreg_read_clock: cap == 0 only, any cap above
+ * is taken); a null op array whose count says it is non-empty; an output
+ * pointer equal to its input pointer. Otherwise n_obj == 0 is CRDT_OK, null
+ * arrays included. An object without ops is copied through, zero-filled to
+ * out_cap.
+ * Latched per object (crdt_ctx_status; the other objects are unaffected, the
+ * object's output is unspecified): CRDT_ECAPACITY when any step of its op
+ * list needs more than out_cap slots (intermediate states count; the drop of
+ * a Put precedes its append); CRDT_ENONCANON for n[i] > cap, obj_end /
+ * clk_end decreasing or past n_ops / n_clk (nothing outside the op arrays is
+ * read), or an op clock with actors not strictly increasing, a zero counter
+ * or an actor >= n_actors.
+ * Registers of out_cap <= 64 slots whose [out_cap][n_actors] block fits 60 KB
+ * of LDS per wave take the fast kernel; the rest a one-wave-per-register
+ * kernel that edits the output block in HBM.                               */
+typedef struct crdt_mvreg_ops {      /* all device arrays */
+  const uint64_t* obj_end;  /* n_obj: object i's ops are [obj_end[i-1], obj_end[i]) */
+  const uint64_t* val;      /* n_ops: the Put's value */
+  const uint64_t* clk_end;  /* n_ops: op j's clock = pairs [clk_end[j-1], clk_end[j]) */
+  const uint32_t* clk_act;  /* n_clk: actors strictly increasing within an op */
+  const uint64_t* clk_ctr;  /* n_clk: non-zero */
+  size_t n_ops, n_clk;
+} crdt_mvreg_ops;
+int crdt_mvreg_apply(crdt_ctx* ctx, const uint32_t* d_self_n, const uint64_t* d_self_clk,
+                     const uint64_t* d_self_val, uint32_t self_cap, const crdt_mvreg_ops* ops,
+                     uint32_t* d_out_n, uint64_t* d_out_clk, uint64_t* d_out_val, uint32_t out_cap,
+                     size_t n_obj, uint32_t n_actors, void* stream);
+int crdt_mvreg_truncate(crdt_ctx* ctx, const uint32_t* d_self_n, const uint64_t* d_self_clk,
+                        const uint64_t* d_self_val, uint32_t self_cap, const uint64_t* d_clock,
+                        uint32_t* d_out_n, uint64_t* d_out_clk, uint64_t* d_out_val, uint32_t out_cap,
+                        size_t n_obj, uint32_t n_actors, void* stream);
+int crdt_mvreg_read_clock(crdt_ctx* ctx, const uint32_t* d_n, const uint64_t* d_clk, uint32_t cap,
+                          uint64_t* d_out_clock, size_t n_obj, uint32_t n_actors, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * Batched op path: CmRDT::apply for Orswot (src/orswot.rs:61-85; Op enum
  * :38-53): out[i] = self[i] after applying object i's ops in order.
  *   Op::Add { dot: (actor, counter), member }   kind CRDT_OP_ADD

@@ -25,7 +25,7 @@ __all__ = [
     "Engine", "OrswotBatch", "GenParams", "CrdtError", "generate_orswot", "generate_dense", "HostOrswot",
     "Orswot", "VClock", "GCounter", "PNCounter", "merge_batch", "decode_record", "encode_record",
     "record_bytes", "CONFIG3", "EXPORTS", "LIB_PATH", "CONFIG5", "SPARSE_CLOCK", "generate_replicas", "ClockBatch",
-    "generate_clocks_csr", "MapMapSlab", "MapOps", "MapMapOps",
+    "generate_clocks_csr", "MapMapSlab", "MapOps", "MapMapOps", "MVRegOps",
 ]
 
 # SURVEY.md §8(d) config 3 / BASELINE.json configs[2].
@@ -273,6 +273,67 @@ class MapOps:
     @classmethod
     def from_lists(cls, per_obj, device=0):
         """per_obj[i] = [("up", actor, counter, key, [(a, c), ...], val) | ("rm", key, [(a, c), ...]) | ("nop",), ...]"""
+        return cls.from_arrays(*cls.arrays_from_lists(per_obj), device=device)
+
+
+class MVRegOps:
+    """A batch of MVReg<u64, A> ops (Op::Put { clock, val }, src/mvreg.rs:51-59)
+    on the device, grouped per object in order (crdt_mvreg_ops)."""
+
+    def __init__(self, obj_end, val, clk_end, clk_act, clk_ctr, max_ops=None):
+        self.t = (obj_end, val, clk_end, clk_act, clk_ctr)
+        self.n_obj = int(obj_end.numel())
+        self.n_ops = int(val.numel())
+        self.n_clk = int(clk_act.numel())
+        self.max_ops = max_ops  # the longest op list, recorded at pack time (None: not known on the host)
+
+    def cops(self):
+        from ._lib import MVRegOpsC
+
+        p = [C.c_void_p(t.data_ptr()) if t.numel() else None for t in self.t]
+        return MVRegOpsC(*p, self.n_ops, self.n_clk)
+
+    @classmethod
+    def from_arrays(cls, obj_end, val, clk_end, clk_act, clk_ctr, device=0):
+        """Host numpy arrays (u64 / u32 as in crdt_mvreg_ops) -> device; not validated."""
+        torch = _torch()
+        dev = f"cuda:{device}"
+
+        def put(x, u32):
+            x = np.ascontiguousarray(np.asarray(x, dtype=np.uint32 if u32 else np.uint64))
+            return torch.from_numpy(x.view(np.int32 if u32 else np.int64)).to(dev)
+
+        ends = np.asarray(obj_end, dtype=np.uint64)
+        # (a decreasing obj_end is the kernel's to reject: its wrapped difference only sizes a default output)
+        grow = int(np.diff(ends, prepend=np.uint64(0)).max()) if ends.size else 0
+        return cls(put(obj_end, False), put(val, False), put(clk_end, False), put(clk_act, True),
+                   put(clk_ctr, False), max_ops=grow)
+
+    @staticmethod
+    def arrays_from_lists(per_obj):
+        """per_obj[i] = [(clock_pairs, val), ...] with clock_pairs = [(actor, counter), ...]
+        -> the five host arrays of crdt_mvreg_ops. A clock must be canonical
+        (actors strictly increasing, counters > 0): ValueError otherwise."""
+        ends, val, cend, cact, cctr = [], [], [], [], []
+        for i, ops in enumerate(per_obj):
+            for pairs, v in ops:
+                prev = -1
+                for a, c in pairs:
+                    if a <= prev:
+                        raise ValueError(f"object {i}: clock actors not strictly increasing: {list(pairs)!r}")
+                    if c <= 0:
+                        raise ValueError(f"object {i}: zero counter in clock {list(pairs)!r}")
+                    prev = a
+                    cact.append(a); cctr.append(c)
+                cend.append(len(cact))
+                val.append(v)
+            ends.append(len(val))
+        return (np.asarray(ends, np.uint64), np.asarray(val, np.uint64), np.asarray(cend, np.uint64),
+                np.asarray(cact, np.uint32), np.asarray(cctr, np.uint64))
+
+    @classmethod
+    def from_lists(cls, per_obj, device=0):
+        """per_obj[i] = [(clock_pairs, val), ...]"""
         return cls.from_arrays(*cls.arrays_from_lists(per_obj), device=device)
 
 
@@ -977,6 +1038,73 @@ class Engine:
         if check_status:
             self.status(stream)
         return outn, outc, outv
+
+    def _mvreg_out(self, n_obj, cap, n_actors, dev, out):
+        torch = _torch()
+        if out is not None:
+            return out
+        return (torch.empty(n_obj, dtype=torch.int32, device=dev),
+                torch.empty((n_obj, cap, n_actors), dtype=torch.int64, device=dev),
+                torch.empty((n_obj, cap), dtype=torch.int64, device=dev))
+
+    def mvreg_apply(self, self_slab, ops: "MVRegOps", n_actors, out_cap=None, out=None, stream=None,
+                    check_status=True):
+        """out[i] = self[i] after MVReg::apply (src/mvreg.rs:158-186) of object i's
+        Puts in order, over slabs as in mvreg_merge; returns the output slab
+        (`out`, or a new one of out_cap slots, default: self's plus one per op
+        of the longest op list, within the call's limit: ops.max_ops, recorded
+        when the batch was packed from host arrays; for an MVRegOps built from
+        device tensors without it, obj_end is copied to the host to find it,
+        which synchronises — pass out or out_cap to avoid that). Not in place."""
+        sn, sc, sv = self_slab
+        n_obj, scap = int(sn.numel()), int(sv.shape[1])
+        if out is not None:
+            out_cap = int(out[2].shape[1])
+        elif out_cap is None:
+            grow = ops.max_ops
+            if grow is None:
+                ends = ops.t[0].cpu().numpy().view(np.uint64) if ops.n_obj else np.zeros(0, np.uint64)
+                grow = int(np.diff(ends, prepend=np.uint64(0)).max()) if ends.size else 0
+            out_cap = min(2048, scap + grow)
+        outn, outc, outv = self._mvreg_out(n_obj, out_cap, n_actors, sn.device, out)
+        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        o = ops.cops()
+        check(lib.crdt_mvreg_apply(self.ctx, p(sn), p(sc), p(sv), scap, C.byref(o), p(outn), p(outc), p(outv),
+                                   out_cap, n_obj, n_actors, self._stream(stream)), "mvreg_apply")
+        if check_status:
+            self.status(stream)
+        return outn, outc, outv
+
+    def mvreg_truncate(self, self_slab, clock_rows, n_actors, out_cap=None, out=None, stream=None,
+                       check_status=True):
+        """Causal::truncate (src/mvreg.rs:100-113) of register i by the dense
+        clock row clock_rows[i] (int64 device tensor [n][n_actors], 0 = absent);
+        returns the output slab (out_cap defaults to self's). Not in place."""
+        sn, sc, sv = self_slab
+        n_obj, scap = int(sn.numel()), int(sv.shape[1])
+        out_cap = int(out[2].shape[1]) if out is not None else (out_cap or scap)
+        outn, outc, outv = self._mvreg_out(n_obj, out_cap, n_actors, sn.device, out)
+        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        check(lib.crdt_mvreg_truncate(self.ctx, p(sn), p(sc), p(sv), scap, p(clock_rows), p(outn), p(outc), p(outv),
+                                      out_cap, n_obj, n_actors, self._stream(stream)), "mvreg_truncate")
+        if check_status:
+            self.status(stream)
+        return outn, outc, outv
+
+    def mvreg_read_clock(self, slab, n_actors, out=None, stream=None, check_status=True):
+        """read().add_clock (src/mvreg.rs:201-222) of every register: the
+        pointwise max of its used clock rows, an int64 device tensor [n][n_actors]."""
+        torch = _torch()
+        sn, sc = slab[0], slab[1]
+        n_obj, cap = int(sn.numel()), int(sc.shape[1])
+        if out is None:
+            out = torch.empty((n_obj, n_actors), dtype=torch.int64, device=sn.device)
+        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        check(lib.crdt_mvreg_read_clock(self.ctx, p(sn), p(sc), cap, p(out), n_obj, n_actors, self._stream(stream)),
+              "mvreg_read_clock")
+        if check_status:
+            self.status(stream)
+        return out
 
     # ------------------------------------------------ Map<u64, MVReg<u64>>
     def map_mvreg_merge(self, S: "MapSlab", O: "MapSlab", n_actors, stream=None, check_status=True, out=None):

@@ -79,6 +79,7 @@ EXPORTS = [
     "crdt_map_map_merge_scratch_bytes", "crdt_map_map_merge", "crdt_replica_allreduce_max_transport",
     "crdt_replica_reduce_scatter_max_transport", "crdt_map_mvreg_apply", "crdt_map_orswot_apply",
     "crdt_map_map_apply_scratch_bytes", "crdt_map_map_apply",
+    "crdt_mvreg_apply", "crdt_mvreg_truncate", "crdt_mvreg_read_clock",
 ]
 
 CRDT_COMM_ID_BYTES = 128
@@ -110,6 +111,12 @@ class MapOpsC(C.Structure):
     """crdt_map_mvreg_ops (include/crdts_hip.h)."""
     _fields_ = [(f, C.c_void_p) for f in ("obj_end", "kind", "key", "actor", "counter", "val", "clk_end", "clk_act",
                                           "clk_ctr")] + [("n_ops", C.c_size_t), ("n_clk", C.c_size_t)]
+
+
+class MVRegOpsC(C.Structure):
+    """crdt_mvreg_ops (include/crdts_hip.h)."""
+    _fields_ = [(f, C.c_void_p) for f in ("obj_end", "val", "clk_end", "clk_act", "clk_ctr")] + \
+               [("n_ops", C.c_size_t), ("n_clk", C.c_size_t)]
 
 
 MAP_MAP_OPS_FIELDS = ("obj_end", "kind", "key", "actor", "counter", "key2", "actor2", "counter2", "val", "clk_end",
@@ -243,6 +250,9 @@ def _load():
         "crdt_orswot_apply": (I, [P, BP, C.POINTER(Ops), U32, U32, P, P, SZ, P]),
         "crdt_vclock_partial_cmp": (I, [P, P, P, SZ, U32, P, P]),
         "crdt_mvreg_merge": (I, [P, P, P, P, U32, P, P, P, U32, P, P, P, U32, SZ, U32, P]),
+        "crdt_mvreg_apply": (I, [P, P, P, P, U32, C.POINTER(MVRegOpsC), P, P, P, U32, SZ, U32, P]),
+        "crdt_mvreg_truncate": (I, [P, P, P, P, U32, P, P, P, P, U32, SZ, U32, P]),
+        "crdt_mvreg_read_clock": (I, [P, P, P, U32, P, SZ, U32, P]),
         "crdt_map_mvreg_merge": (I, [P, C.POINTER(MapSlabC), C.POINTER(MapSlabC), C.POINTER(MapSlabC), SZ, U32, P]),
         "crdt_map_mvreg_apply": (I, [P, C.POINTER(MapSlabC), C.POINTER(MapOpsC), C.POINTER(MapSlabC), SZ, U32, P]),
         "crdt_map_orswot_merge": (I, [P, C.POINTER(MapOrswotSlabC), C.POINTER(MapOrswotSlabC),

@@ -570,6 +570,52 @@ int crdt_mvreg_merge(crdt_ctx* ctx, const uint32_t* d_self_n, const uint64_t* d_
                             S(stream));
 }
 
+static bool mvreg_op_caps_ok(uint32_t self_cap, uint32_t out_cap, uint32_t n_actors) {
+  return n_actors && self_cap && self_cap <= 1024 && out_cap >= self_cap && out_cap <= 2048;
+}
+
+int crdt_mvreg_apply(crdt_ctx* ctx, const uint32_t* d_self_n, const uint64_t* d_self_clk, const uint64_t* d_self_val,
+                     uint32_t self_cap, const crdt_mvreg_ops* ops, uint32_t* d_out_n, uint64_t* d_out_clk,
+                     uint64_t* d_out_val, uint32_t out_cap, size_t n_obj, uint32_t n_actors, void* stream) {
+  if (!ctx || !ops || !mvreg_op_caps_ok(self_cap, out_cap, n_actors)) return CRDT_EINVAL;
+  if (n_obj) {
+    if (!d_self_n || !d_self_clk || !d_self_val || !d_out_n || !d_out_clk || !d_out_val || !ops->obj_end)
+      return CRDT_EINVAL;
+    if (d_out_n == d_self_n || d_out_clk == d_self_clk || d_out_val == d_self_val) return CRDT_EINVAL;  // not in place
+  }
+  if (ops->n_ops && (!ops->val || !ops->clk_end)) return CRDT_EINVAL;
+  if (ops->n_clk && (!ops->clk_act || !ops->clk_ctr)) return CRDT_EINVAL;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_mvreg_apply(d_self_n, d_self_clk, d_self_val, self_cap, *ops, d_out_n, d_out_clk, d_out_val, out_cap,
+                            n_obj, n_actors, ctx->d_status, S(stream));
+}
+
+int crdt_mvreg_truncate(crdt_ctx* ctx, const uint32_t* d_self_n, const uint64_t* d_self_clk,
+                        const uint64_t* d_self_val, uint32_t self_cap, const uint64_t* d_clock, uint32_t* d_out_n,
+                        uint64_t* d_out_clk, uint64_t* d_out_val, uint32_t out_cap, size_t n_obj, uint32_t n_actors,
+                        void* stream) {
+  if (!ctx || !mvreg_op_caps_ok(self_cap, out_cap, n_actors)) return CRDT_EINVAL;
+  if (n_obj) {
+    if (!d_self_n || !d_self_clk || !d_self_val || !d_clock || !d_out_n || !d_out_clk || !d_out_val)
+      return CRDT_EINVAL;
+    if (d_out_n == d_self_n || d_out_clk == d_self_clk || d_out_val == d_self_val) return CRDT_EINVAL;  // not in place
+  }
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_mvreg_truncate(d_self_n, d_self_clk, d_self_val, self_cap, d_clock, d_out_n, d_out_clk, d_out_val,
+                               out_cap, n_obj, n_actors, ctx->d_status, S(stream));
+}
+
+int crdt_mvreg_read_clock(crdt_ctx* ctx, const uint32_t* d_n, const uint64_t* d_clk, uint32_t cap,
+                          uint64_t* d_out_clock, size_t n_obj, uint32_t n_actors, void* stream) {
+  if (!ctx || n_actors == 0 || cap == 0) return CRDT_EINVAL;
+  if (n_obj && (!d_n || !d_clk || !d_out_clock || d_out_clock == d_clk)) return CRDT_EINVAL;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_mvreg_read_clock(d_n, d_clk, cap, d_out_clock, n_obj, n_actors, ctx->d_status, S(stream));
+}
+
 int crdt_map_mvreg_merge(crdt_ctx* ctx, const crdt_map_mvreg_slab* self, const crdt_map_mvreg_slab* other,
                          const crdt_map_mvreg_slab* out, size_t n_obj, uint32_t n_actors, void* stream) {
   if (!ctx || !self || !other || !out || n_actors == 0 || n_actors > 128) return CRDT_EINVAL;

@@ -76,6 +76,17 @@ int launch_mvreg_merge(const uint32_t* sn, const uint64_t* sclk, const uint64_t*
                        uint64_t* outclk, uint64_t* outval, uint32_t outcap, uint64_t n_obj, uint32_t A, int* status,
                        hipStream_t stream);
 
+// MVReg op path (mvreg_apply.hip): Put lists, truncate, the read clock;
+// self_cap <= out_cap within the ABI limits (api.hip)
+int launch_mvreg_apply(const uint32_t* sn, const uint64_t* sclk, const uint64_t* sval, uint32_t scap,
+                       const crdt_mvreg_ops& P, uint32_t* outn, uint64_t* outclk, uint64_t* outval, uint32_t outcap,
+                       uint64_t n_obj, uint32_t A, int* status, hipStream_t stream);
+int launch_mvreg_truncate(const uint32_t* sn, const uint64_t* sclk, const uint64_t* sval, uint32_t scap,
+                          const uint64_t* clock, uint32_t* outn, uint64_t* outclk, uint64_t* outval, uint32_t outcap,
+                          uint64_t n_obj, uint32_t A, int* status, hipStream_t stream);
+int launch_mvreg_read_clock(const uint32_t* sn, const uint64_t* sclk, uint32_t scap, uint64_t* out, uint64_t n_obj,
+                            uint32_t A, int* status, hipStream_t stream);
+
 int launch_map_mvreg_merge(const crdt_map_mvreg_slab& S, const crdt_map_mvreg_slab& O, const crdt_map_mvreg_slab& R,
                            uint64_t n_obj, uint32_t A, int* status, uint32_t* ctl, hipStream_t stream, int variant = 0);
 // Map<u64, MVReg>::apply (map_apply.hip): R row i = S row i after its ops of P
