@@ -867,6 +867,66 @@ int crdt_map_orswot_apply(crdt_ctx* ctx, const crdt_map_orswot_slab* self, const
                           const crdt_map_orswot_slab* out, size_t n_obj, uint32_t n_actors, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * Causal::truncate of the three Map types, batched (src/map.rs:131-158):
+ * out[i] := self[i] after Map::truncate(d_clock[i]), d_clock dense
+ * [n_obj][n_actors] with 0 = absent (as crdt_mvreg_truncate), in the slab's
+ * canonical form (keys ascending, nested values in their own canonical form,
+ * deferred clocks in CLOCK ORDER, sets ascending). Only the used slots of out
+ * are written (the inner rows of unused key slots of a nested map not at
+ * all). Not in place. With T = d_clock[i]:
+ *  - Entry clocks (:134-141): every entry clock loses T — each actor whose
+ *    counter is <= T's (VClock::subtract, src/vclock.rs:236-242). An entry
+ *    whose clock becomes empty is dropped. Any other entry's value takes its
+ *    own truncate(T):
+ *      MVReg::truncate (src/mvreg.rs:100-113): every value clock loses T, an
+ *        emptied value is dropped, order kept; an entry may be left with zero
+ *        values.
+ *      Orswot::truncate (src/orswot.rs:159-172), as in crdt_map_orswot_merge
+ *        and crdt_map_orswot_apply: members whose clock is <= T are dropped;
+ *        the set's clock is joined with T; the set's apply_deferred runs under
+ *        that clock, retiring the deferred clocks it now covers after removing
+ *        their members; T is subtracted from the set's clock and from every
+ *        member clock — a member clock emptied by that last step stays, as an
+ *        all-zero row. The set's deferred clocks are not subtracted.
+ *      Map::truncate, these same rules, for the nested map.
+ *  - Map deferred clocks (:147-154): every deferred clock loses T; an emptied
+ *    one is dropped; the rest go back into CLOCK ORDER (the subtract can
+ *    reorder them). Where two become equal the key set of the later one —
+ *    CLOCK ORDER before the subtract — replaces the earlier one's, the rule of
+ *    crdt_map_map_merge and crdt_map_map_apply (the reference inserts into a
+ *    HashMap there).
+ *  - Map clock (:156): the map clock loses T.
+ *  - The reference runs no apply_deferred in truncate, and none runs here.
+ *  - An all-zero T is the identity.
+ *
+ * crdt_map_map_truncate's d_scratch: crdt_map_map_truncate_scratch_bytes(out,
+ * n_obj, n_actors) bytes, 16-byte aligned (per out key slot, the self inner
+ * map it holds).
+ *
+ * CRDT_EINVAL (before any device work): a null ctx / self / out; a null
+ * d_clock with n_obj > 0; n_actors == 0 or > 128; self capacities outside the
+ * matching merge's per-side limits; an out capacity below self's or above the
+ * matching apply's out limits; a null slab array with n_obj > 0; out->clock
+ * == self->clock (no out array may overlap a self array); for the nested call
+ * a null, misaligned or too small scratch with n_obj > 0; for Map<K, Orswot>
+ * a per-wave workspace — one nested set of SELF's capacities, by
+ * crdt_map_orswot_apply's formula: 8 * (mcap * (1 + n_actors) + vdcap *
+ * (n_actors + vscap)) + 4 * (mcap + 2 * vdcap) bytes — above that call's
+ * 60672 bytes. n_obj == 0 is CRDT_OK, null arrays included.
+ * Latched per object (the other objects are unaffected, the object's output
+ * row is unspecified): CRDT_ENONCANON for a count above its capacity, inner
+ * maps included. Truncation never grows a count, so with out capacities >=
+ * self's no object can latch CRDT_ECAPACITY.                                */
+int crdt_map_mvreg_truncate(crdt_ctx* ctx, const crdt_map_mvreg_slab* self, const uint64_t* d_clock,
+                            const crdt_map_mvreg_slab* out, size_t n_obj, uint32_t n_actors, void* stream);
+int crdt_map_orswot_truncate(crdt_ctx* ctx, const crdt_map_orswot_slab* self, const uint64_t* d_clock,
+                             const crdt_map_orswot_slab* out, size_t n_obj, uint32_t n_actors, void* stream);
+size_t crdt_map_map_truncate_scratch_bytes(const crdt_map_map_slab* out, size_t n_obj, uint32_t n_actors);
+int crdt_map_map_truncate(crdt_ctx* ctx, const crdt_map_map_slab* self, const uint64_t* d_clock,
+                          const crdt_map_map_slab* out, size_t n_obj, uint32_t n_actors, void* d_scratch,
+                          size_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * VClock partial order and MVReg merge, batched.
  * crdt_vclock_partial_cmp: d_out[i] = partial_cmp(a[i], b[i])
  * (src/vclock.rs:59-71) over dense rows u64[n][n_actors], 0 = absent:

@@ -1244,6 +1244,69 @@ class Engine:
             self.status(stream)
         return out
 
+    # ------------------------------------------------ Map::truncate, the three Map types
+    def map_mvreg_truncate(self, S: "MapSlab", clock_rows, n_actors, out_caps=None, out=None, stream=None,
+                           check_status=True):
+        """out[i] = S[i] after Map::truncate (src/map.rs:131-158) by the dense
+        clock row clock_rows[i] (int64 device tensor [n][n_actors], 0 = absent);
+        returns the output slab (`out`, or a new one of capacities out_caps =
+        (kcap, mcap, dcap, scap), default: S's). Only the used slots of the
+        output are written. Not in place."""
+        n = int(S.a["n_keys"].shape[0])
+        if out is None:
+            out = MapSlab.alloc(n, n_actors, *(out_caps or (S.kcap, S.mcap, S.dcap, S.scap)),
+                                device=S.a["clock"].device)
+        s, r = S.cstruct(), out.cstruct()
+        check(lib.crdt_map_mvreg_truncate(self.ctx, C.byref(s), C.c_void_p(clock_rows.data_ptr()), C.byref(r), n,
+                                          n_actors, self._stream(stream)), "map_mvreg_truncate")
+        if check_status:
+            self.status(stream)
+        return out
+
+    def map_orswot_truncate(self, S: "MapOrswotSlab", clock_rows, n_actors, out_caps=None, out=None, stream=None,
+                            check_status=True):
+        """out[i] = S[i] after Map::truncate (src/map.rs:131-158, the sets by
+        Orswot::truncate, src/orswot.rs:159-172) by clock_rows[i]; returns the
+        output slab (`out`, or a new one of capacities out_caps = dict(kcap,
+        mcap, vdcap, vscap, dcap, scap), default: S's). Only the used slots of
+        the output are written. Not in place."""
+        n = S.n
+        if out is None:
+            out = MapOrswotSlab.alloc(n, n_actors, device=S.a["clock"].device, **(out_caps or S.caps))
+        s, r = S.cstruct(), out.cstruct()
+        check(lib.crdt_map_orswot_truncate(self.ctx, C.byref(s), C.c_void_p(clock_rows.data_ptr()), C.byref(r), n,
+                                           n_actors, self._stream(stream)), "map_orswot_truncate")
+        if check_status:
+            self.status(stream)
+        return out
+
+    def map_map_truncate(self, S: "MapMapSlab", clock_rows, n_actors, out_caps=None, inner_out_caps=None, out=None,
+                         stream=None, check_status=True):
+        """out[i] = S[i] after Map::truncate (src/map.rs:131-158, the inner maps
+        by the same truncate) by clock_rows[i]; returns the output slab (`out`,
+        or a new one of capacities out_caps = (kcap, dcap, scap) and
+        inner_out_caps = (kcap, mcap, dcap, scap), default: S's). Only the
+        used slots of the output are written. Not in place."""
+        torch = _torch()
+        n = S.n
+        dev = S.a["clock"].device
+        if out is None:
+            out = MapMapSlab.alloc(n, n_actors, *(out_caps or (S.kcap, S.dcap, S.scap)),
+                                   tuple(inner_out_caps or S.inner_caps), device=dev)
+        s, r = S.cstruct(), out.cstruct()
+        nb = int(lib.crdt_map_map_truncate_scratch_bytes(C.byref(r), n, n_actors))
+        # the engine keeps the scratch (grown as needed): a launch in flight on
+        # another stream never sees it freed
+        sc = getattr(self, "_map_map_truncate_scratch", None)
+        if sc is None or sc.numel() < nb or sc.device != dev:
+            sc = self._map_map_truncate_scratch = torch.empty(max(16, nb), dtype=torch.uint8, device=dev)
+        check(lib.crdt_map_map_truncate(self.ctx, C.byref(s), C.c_void_p(clock_rows.data_ptr()), C.byref(r), n,
+                                        n_actors, C.c_void_p(sc.data_ptr()), int(sc.numel()), self._stream(stream)),
+              "map_map_truncate")
+        if check_status:
+            self.status(stream)
+        return out
+
     # ------------------------------------------------ batched op path
     def orswot_apply(self, B: "OrswotBatch", ops: "OrswotOps", stream=None, check_status=True):
         """out[i] = B[i] after CmRDT::apply of object i's ops in order

@@ -80,6 +80,8 @@ EXPORTS = [
     "crdt_replica_reduce_scatter_max_transport", "crdt_map_mvreg_apply", "crdt_map_orswot_apply",
     "crdt_map_map_apply_scratch_bytes", "crdt_map_map_apply",
     "crdt_mvreg_apply", "crdt_mvreg_truncate", "crdt_mvreg_read_clock",
+    "crdt_map_mvreg_truncate", "crdt_map_orswot_truncate", "crdt_map_map_truncate_scratch_bytes",
+    "crdt_map_map_truncate",
 ]
 
 CRDT_COMM_ID_BYTES = 128
@@ -265,6 +267,10 @@ def _load():
         "crdt_map_map_apply_scratch_bytes": (SZ, [C.POINTER(MapMapSlabC), SZ, U32]),
         "crdt_map_map_apply": (I, [P, C.POINTER(MapMapSlabC), C.POINTER(MapMapOpsC), C.POINTER(MapMapSlabC), SZ,
                                    U32, P, SZ, P]),
+        "crdt_map_mvreg_truncate": (I, [P, C.POINTER(MapSlabC), P, C.POINTER(MapSlabC), SZ, U32, P]),
+        "crdt_map_orswot_truncate": (I, [P, C.POINTER(MapOrswotSlabC), P, C.POINTER(MapOrswotSlabC), SZ, U32, P]),
+        "crdt_map_map_truncate_scratch_bytes": (SZ, [C.POINTER(MapMapSlabC), SZ, U32]),
+        "crdt_map_map_truncate": (I, [P, C.POINTER(MapMapSlabC), P, C.POINTER(MapMapSlabC), SZ, U32, P, SZ, P]),
         "crdt_comm_unique_id": (I, [P]),
         "crdt_comm_init": (I, [P, P, I, I]),
         "crdt_comm_destroy": (I, [P]),

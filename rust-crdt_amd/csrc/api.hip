@@ -792,4 +792,67 @@ int crdt_map_orswot_apply(crdt_ctx* ctx, const crdt_map_orswot_slab* self, const
   return launch_map_orswot_apply(*self, *ops, *out, n_obj, n_actors, ctx->d_status, ctx->d_ctl, S(stream));
 }
 
+int crdt_map_mvreg_truncate(crdt_ctx* ctx, const crdt_map_mvreg_slab* self, const uint64_t* d_clock,
+                            const crdt_map_mvreg_slab* out, size_t n_obj, uint32_t n_actors, void* stream) {
+  if (!ctx || !self || !out || n_actors == 0 || n_actors > 128) return CRDT_EINVAL;
+  if (!map_mvreg_caps_ok(self)) return CRDT_EINVAL;
+  // crdt_map_mvreg_apply's out limits
+  if (out->kcap < self->kcap || out->kcap > 8192 || out->mcap < self->mcap || out->mcap > 256 ||
+      out->dcap < self->dcap || out->dcap > 128 || out->scap < self->scap || out->scap > 8192)
+    return CRDT_EINVAL;
+  if (n_obj) {
+    if (!d_clock || !map_mvreg_ptrs_ok(self) || !map_mvreg_ptrs_ok(out)) return CRDT_EINVAL;
+    if (out->clock == self->clock) return CRDT_EINVAL;  // not in place
+  }
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_map_mvreg_truncate(*self, d_clock, *out, n_obj, n_actors, ctx->d_status, ctx->d_ctl, S(stream));
+}
+
+int crdt_map_orswot_truncate(crdt_ctx* ctx, const crdt_map_orswot_slab* self, const uint64_t* d_clock,
+                             const crdt_map_orswot_slab* out, size_t n_obj, uint32_t n_actors, void* stream) {
+  if (!ctx || !self || !out || n_actors == 0 || n_actors > 128) return CRDT_EINVAL;
+  // crdt_map_orswot_merge's per-side limits
+  if (self->kcap == 0 || self->kcap > 4096 || self->mcap == 0 || self->mcap > 256 || self->vdcap == 0 ||
+      self->vdcap > 256 || self->vscap == 0 || self->vscap > 256 || self->dcap == 0 || self->dcap > 256 ||
+      self->scap == 0 || self->scap > 4096)
+    return CRDT_EINVAL;
+  // crdt_map_orswot_apply's out limits
+  if (out->kcap < self->kcap || out->kcap > 8192 || out->mcap < self->mcap || out->mcap > 512 ||
+      out->vdcap < self->vdcap || out->vdcap > 512 || out->vscap < self->vscap || out->vscap > 512 ||
+      out->dcap < self->dcap || out->dcap > 512 || out->scap < self->scap || out->scap > 8192)
+    return CRDT_EINVAL;
+  // the kernel's workspace: one nested set of self's capacities
+  if (map_orswot_apply_lds_bytes(*self, n_actors) > kMapOrswotApplyLdsMax) return CRDT_EINVAL;
+  if (n_obj) {
+    if (!d_clock || !map_orswot_ptrs_ok(self) || !map_orswot_ptrs_ok(out)) return CRDT_EINVAL;
+    if (out->clock == self->clock) return CRDT_EINVAL;  // not in place
+  }
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_map_orswot_truncate(*self, d_clock, *out, n_obj, n_actors, ctx->d_status, ctx->d_ctl, S(stream));
+}
+
+size_t crdt_map_map_truncate_scratch_bytes(const crdt_map_map_slab* out, size_t n_obj, uint32_t n_actors) {
+  return out ? map_map_truncate_scratch_bytes(*out, n_obj, n_actors) : 0u;
+}
+
+int crdt_map_map_truncate(crdt_ctx* ctx, const crdt_map_map_slab* self, const uint64_t* d_clock,
+                          const crdt_map_map_slab* out, size_t n_obj, uint32_t n_actors, void* d_scratch,
+                          size_t scratch_bytes, void* stream) {
+  if (!ctx || !self || !out || n_actors == 0 || n_actors > 128) return CRDT_EINVAL;
+  if (!map_map_apply_caps_ok(self, out)) return CRDT_EINVAL;  // crdt_map_map_apply's limits, self and out
+  if (n_obj) {
+    if (!d_clock || !map_map_ptrs_ok(self) || !map_map_ptrs_ok(out)) return CRDT_EINVAL;
+    if (out->clock == self->clock || out->inner.clock == self->inner.clock) return CRDT_EINVAL;  // not in place
+    if (!d_scratch || ((uintptr_t)d_scratch & 15u) ||
+        scratch_bytes < map_map_truncate_scratch_bytes(*out, n_obj, n_actors))
+      return CRDT_EINVAL;
+  }
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_map_map_truncate(*self, d_clock, *out, n_obj, n_actors, (uint8_t*)d_scratch, ctx->d_status,
+                                 ctx->d_ctl, S(stream));
+}
+
 }  // extern "C"

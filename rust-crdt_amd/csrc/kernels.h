@@ -123,4 +123,18 @@ int launch_map_orswot_apply(const crdt_map_orswot_slab& S, const crdt_map_orswot
 size_t map_orswot_apply_lds_bytes(const crdt_map_orswot_slab& R, uint32_t A);
 constexpr size_t kMapOrswotApplyLdsMax = 65536 - 4864;  // 64 KB less the kernel's static op stage and key mirror
 
+// Map::truncate of the three Map types (map_truncate.hip): R row i = S row i
+// after Map::truncate(clk row i), clk dense [n_obj][A]; R's capacities >= S's,
+// R != S (api.hip). Map<u64, Orswot>: the workspace, map_orswot_apply_lds_bytes
+// of S, within kMapOrswotApplyLdsMax. The nested map: scratch of
+// map_map_truncate_scratch_bytes(R, ..) bytes, 16-byte aligned.
+int launch_map_mvreg_truncate(const crdt_map_mvreg_slab& S, const uint64_t* clk, const crdt_map_mvreg_slab& R,
+                              uint64_t n_obj, uint32_t A, int* status, uint32_t* ctl, hipStream_t stream);
+int launch_map_orswot_truncate(const crdt_map_orswot_slab& S, const uint64_t* clk, const crdt_map_orswot_slab& R,
+                               uint64_t n_obj, uint32_t A, int* status, uint32_t* ctl, hipStream_t stream);
+size_t map_map_truncate_scratch_bytes(const crdt_map_map_slab& R, uint64_t n_obj, uint32_t A);
+int launch_map_map_truncate(const crdt_map_map_slab& S, const uint64_t* clk, const crdt_map_map_slab& R,
+                            uint64_t n_obj, uint32_t A, uint8_t* scratch, int* status, uint32_t* ctl,
+                            hipStream_t stream);
+
 }  // namespace crdts_hip

@@ -451,5 +451,122 @@ __device__ inline void map_truncate(const MapRef& m, MapSt<NS>& st, const Row<NS
   mw_sync();
 }
 
+// ---- Map::truncate from one slab row into another (source != destination):
+// the source's used slots are read once and only the survivors are written.
+
+// The deferred part of Map::truncate(T) (src/map.rs:147-154): the n source
+// entries (clocks sdcl[.][A] in CLOCK ORDER, set sizes sdsn, sets sdse[.][sRs])
+// less T into the empty list `d` (d.Rd >= n, d.Rs >= sRs), by map_truncate's
+// rule: an emptied clock is dropped, the rest go to their CLOCK ORDER place,
+// and of two that become equal the later one (CLOCK ORDER before the
+// subtract) stays. The order is worked out on source indices in `ord` (LDS, n
+// slots; the wave's own) and every kept entry is then written once, its used
+// slots only. Returns the count written. Every set size must be <= sRs. Ends
+// in mw_sync().
+template <int NS>
+__device__ inline uint32_t def_truncate_to(const uint64_t* sdcl, const uint32_t* sdsn, const uint64_t* sdse,
+                                           uint32_t sRs, uint32_t n, const DefRef& d, const Row<NS>& T, uint32_t* ord,
+                                           uint32_t A, uint32_t lane) {
+  uint32_t wd = 0;
+  mw_sync();  // the previous list's readers of ord are done
+  for (uint32_t e = 0; e < n; ++e) {
+    const Row<NS> D = vsub(ldrow<NS>(sdcl + (uint64_t)e * A, A, lane), T);
+    if (!vany(D)) continue;
+    uint32_t p = wd;  // its place: above every kept clock it follows
+    bool dup = false;
+    while (p > 0u) {
+      const uint32_t f = uni32(ord[p - 1u]);
+      const int o = vorder(D, vsub(ldrow<NS>(sdcl + (uint64_t)f * A, A, lane), T), lane);
+      if (o > 0) break;
+      if (o == 0) {
+        dup = true;
+        break;
+      }
+      --p;
+    }
+    if (dup) {
+      mw_sync();
+      if (lane == 0u) ord[p - 1u] = e;  // it takes the equal clock's place
+    } else {
+      for (uint32_t hi = wd; hi > p;) {  // the ones above it one slot up, the last 64 first
+        const uint32_t lo = hi - p > kW ? hi - kW : p;
+        const uint32_t k = lo + lane;
+        uint32_t x = 0u;
+        if (k < hi) x = ord[k];
+        mw_sync();
+        if (k < hi) ord[k + 1u] = x;
+        mw_sync();
+        hi = lo;
+      }
+      if (lane == 0u) ord[p] = e;
+      ++wd;
+    }
+    mw_sync();
+  }
+  for (uint32_t j = 0; j < wd; ++j) {
+    const uint32_t e = uni32(ord[j]);
+    const uint32_t sn = uni32(sdsn[e]);
+    strow<NS>(d.dcl + (uint64_t)j * A, vsub(ldrow<NS>(sdcl + (uint64_t)e * A, A, lane), T), A, lane);
+    copy_n(d.dse + (uint64_t)j * d.Rs, sdse + (uint64_t)e * sRs, sn, lane);
+    if (lane == 0u) d.dsn[j] = sn;
+  }
+  mw_sync();
+  return wd;
+}
+
+// Row rrow of R = row srow of S after Map::truncate(T) (src/map.rs:131-158),
+// R's capacities >= S's and R != S: map_truncate's forward compaction with the
+// reads on S and the writes on R (slot w <= k), so nothing is written twice.
+// `ord`: S.dcap LDS slots (def_truncate_to). false, and nothing written, for a
+// row the merge rejects (a count above its capacity). Ends in mw_sync().
+template <int NS>
+__device__ inline bool map_truncate_to(const crdt_map_mvreg_slab& S, uint64_t srow, const crdt_map_mvreg_slab& R,
+                                       uint64_t rrow, const Row<NS>& T, uint32_t* ord, uint32_t A, uint32_t lane) {
+  const uint32_t nS = uni32(S.n_keys[srow]), dS = uni32(S.n_def[srow]);
+  if (nS > S.kcap || dS > S.dcap) return false;
+  const uint32_t vnS = lane < nS ? S.mv_n[srow * S.kcap + lane] : 0u;
+  const uint32_t dnS = lane < dS ? S.dset_n[srow * S.dcap + lane] : 0u;
+  bool bad = vnS > S.mcap || dnS > S.scap;
+  for (uint32_t k = lane + kW; k < nS; k += kW) bad = bad || S.mv_n[srow * S.kcap + k] > S.mcap;
+  for (uint32_t d = lane + kW; d < dS; d += kW) bad = bad || S.dset_n[srow * S.dcap + d] > S.scap;
+  if (__ballot(bad) != 0ull) return false;
+  const MapRef m = map_ref(R, rrow, A);
+  const uint64_t Rm = m.Rm, Sm = S.mcap;
+  const uint64_t* const skeys = S.keys + srow * S.kcap;
+  const uint64_t* const secl = S.eclock + srow * S.kcap * A;
+  const uint64_t* const smvc = S.mv_clock + srow * S.kcap * Sm * A;
+  const uint64_t* const smvv = S.mv_val + srow * S.kcap * Sm;
+  const uint64_t kreg = lane < nS ? skeys[lane] : 0ull;  // lane k: key k (the first 64)
+  uint32_t w = 0;
+  for (uint32_t k = 0; k < nS; ++k) {
+    const Row<NS> ec = vsub(ldrow<NS>(secl + (uint64_t)k * A, A, lane), T);
+    if (!vany(ec)) continue;
+    strow<NS>(m.ecl + (uint64_t)w * A, ec, A, lane);
+    const uint32_t n = k < kW ? (uint32_t)__builtin_amdgcn_readlane(vnS, k) : uni32(S.mv_n[srow * S.kcap + k]);
+    uint32_t wv = 0;
+    for (uint32_t v = 0; v < n; ++v) {
+      const Row<NS> r = vsub(ldrow<NS>(smvc + (k * Sm + v) * A, A, lane), T);
+      if (!vany(r)) continue;
+      strow<NS>(m.mvc + (w * Rm + wv) * A, r, A, lane);
+      if (lane == 0u) m.mvv[w * Rm + wv] = smvv[k * Sm + v];
+      ++wv;
+    }
+    const uint64_t key = k < kW ? lane64(kreg, k) : uni64(skeys[k]);
+    if (lane == 0u) {
+      m.mvn[w] = wv;
+      m.keys[w] = key;
+    }
+    ++w;
+  }
+  const uint32_t wd = def_truncate_to<NS>(S.dclock + srow * S.dcap * A, S.dset_n + srow * S.dcap,
+                                          S.dset + srow * S.dcap * S.scap, S.scap, dS, m.def, T, ord, A, lane);
+  MapSt<NS> st;
+  st.cM = vsub(ldrow<NS>(S.clock + srow * A, A, lane), T);
+  st.nk = w;
+  st.nd = wd;
+  map_close<NS>(m, st, A, lane);
+  return true;
+}
+
 }  // namespace mapws
 }  // namespace crdts_hip
