@@ -26,10 +26,11 @@ def _clock(row):
     return crdts_ref.VClock([(a, int(c)) for a, c in enumerate(row) if c])
 
 
-def orswot_map_to_row(m, S, i, A):
-    """Write a crdts_ref.Map of Orswot values as row i of a host MapOrswotSlab."""
+def orswot_map_to_row(m, S, i, A, zero=True):
+    """Write a crdts_ref.Map of Orswot values as row i of a host MapOrswotSlab
+    (zero=False: the row is known to be all zero, as in a new slab)."""
     a, cp = S.a, S.caps
-    for f in a:
+    for f in a if zero else ():
         a[f][i] = 0
     a["clock"][i] = _row(m.clock, A)
     keys = sorted(m.entries)
@@ -84,10 +85,11 @@ def orswot_map_from_row(S, i):
     return m
 
 
-def mvreg_map_to_row(m, S, i, A):
-    """Write a crdts_ref.Map of MVReg values as row i of a host MapSlab (values in Vec order)."""
+def mvreg_map_to_row(m, S, i, A, zero=True):
+    """Write a crdts_ref.Map of MVReg values as row i of a host MapSlab (values in Vec order;
+    zero=False: the row is known to be all zero, as in a new slab)."""
     a = S.a
-    for f in a:
+    for f in a if zero else ():
         a[f][i] = 0
     a["clock"][i] = _row(m.clock, A)
     keys = sorted(m.entries)
@@ -125,25 +127,26 @@ def mvreg_map_from_row(S, i):
     return m
 
 
-def nested_map_to_row(m, S, i, A):
+def nested_map_to_row(m, S, i, A, zero=True):
     """Write a crdts_ref.Map of Map<u64, MVReg> values (the reference's
     TestMap) as row i of a host MapMapSlab: the outer map's arrays, and key
-    slot k's nested map as inner object i * kcap + k."""
+    slot k's nested map as inner object i * kcap + k (zero=False: the row and
+    its inner maps are known to be all zero, as in a new slab)."""
     a = S.a
-    for f in a:
+    for f in a if zero else ():
         a[f][i] = 0
     a["clock"][i] = _row(m.clock, A)
     keys = sorted(m.entries)
     assert len(keys) <= S.kcap and len(m.deferred) <= S.dcap
     a["n_keys"][i] = len(keys)
-    for k in range(S.kcap):
+    for k in range(S.kcap if zero else 0):
         for f in S.inner.a:
             S.inner.a[f][i * S.kcap + k] = 0
     for k, key in enumerate(keys):
         ec, v = m.entries[key]
         a["keys"][i, k] = key
         a["eclock"][i, k] = _row(ec, A)
-        mvreg_map_to_row(v, S.inner, i * S.kcap + k, A)
+        mvreg_map_to_row(v, S.inner, i * S.kcap + k, A, zero)
     defs = crdts_ref.clock_order(list(m.deferred))
     a["n_def"][i] = len(defs)
     for d, c in enumerate(defs):

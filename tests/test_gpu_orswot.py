@@ -124,6 +124,60 @@ def test_prop_merge_converges_on_gpu(gpu, oracle):
     assert all(len(s) == 1 for s in by_vec.values())
 
 
+def test_prop_merge_converges_witnesses_built_on_gpu(gpu, oracle):
+    """The same property on the same draws with the witnesses built on the
+    device too: witness k of every (opvec, i) fold is one crdt_orswot_apply
+    launch from empty records with that witness's ops in order (a fold with
+    fewer witnesses gets no ops there: its record stays the empty 'defer
+    plunger'), and the fold merges those device batches as they are, each
+    merge's output the next one's input. Every witness equals the oracle's
+    record, every fold step the oracle's fold, and the folds of one vector
+    converge."""
+    import crdts_hip
+
+    A = 100
+    rng = random.Random(2024)
+    opvecs = [opgen.orswot_opvec(rng) for _ in range(60)]
+    folds = [(v, i) for v in range(len(opvecs)) for i in range(2, 11)]
+    ow = []  # per fold: the oracle's witnesses
+    for v, i in folds:
+        w = [oracle.OracleOrswot() for _ in range(i)]
+        for actor, op in opvecs[v]:
+            if op[0] == "add":
+                w[actor % i].apply_add(op[1], op[2], op[3])
+            else:
+                w[actor % i].apply_rm(op[1], op[2])
+        ow.append(w)
+
+    def kernel_op(op):  # Dot{actor, 0}.into() is the empty clock: a canonical op clock holds no zero counter
+        return op if op[0] == "add" else ("rm", op[1], [(a, c) for a, c in op[2] if c])
+
+    empty = crdts_hip.HostOrswot().encode(A)
+    assert any(op[0] == "rm" and op[2][0][1] == 0 for ops in opvecs for _, op in ops)
+    witnesses = []  # step k: the device batch of every fold's witness k
+    for k in range(11):
+        per = [[kernel_op(op) for actor, op in opvecs[v] if k < i and actor % i == k] for v, i in folds]
+        W = gpu.orswot_apply(crdts_hip.OrswotBatch.from_records([empty] * len(folds), A),
+                             crdts_hip.OrswotOps.from_lists(per))
+        for f, (rec, (v, i)) in enumerate(zip(W.records(), folds)):
+            exp = ow[f][k].encode(A) if k < i else empty
+            assert rec == exp, f"witness {k} of fold {(v, i)}"
+        witnesses.append(W)
+    assert sum(len(records.decode(r)["deferred"]) > 0 for r in witnesses[0].records()) > 20
+    merged = crdts_hip.OrswotBatch.from_records([empty] * len(folds), A)
+    omerged = [oracle.OracleOrswot() for _ in folds]
+    for k, W in enumerate(witnesses):
+        merged = gpu.orswot_merge(merged, W)  # device batches, as the kernels left them
+        got = merged.records()
+        for f, (v, i) in enumerate(folds):
+            omerged[f].merge(ow[f][k] if k < i else oracle.OracleOrswot())
+            assert got[f] == omerged[f].encode(A), f"fold {(v, i)} step {k}"
+    by_vec = {}
+    for f, (v, i) in enumerate(folds):
+        by_vec.setdefault(v, set()).add(got[f])
+    assert all(len(s) == 1 for s in by_vec.values())
+
+
 # ------------------------------------------------------------------ config 3 differential
 def test_config3_differential_200k(gpu, oracle):
     import crdts_hip

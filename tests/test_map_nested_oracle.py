@@ -15,6 +15,7 @@ import random
 import pytest
 
 import map_kat_runner as mkr
+from map_exchange import build_opvec, distinct, rand_opvec  # noqa: F401  (the generators: shared with the op-exchange harness)
 
 CASES = mkr.load_cases(nested=True)
 
@@ -31,48 +32,11 @@ def test_nested_cases_present():
             "test_idempotent_quickcheck1", "test_nop_on_new_map_should_remain_a_new_map"} <= names
 
 
-def build_opvec(actor, prims):
-    """test/map.rs:13-46: op i's clock is Dot {actor, i}.into() (empty for
-    i = 0: witness of counter 0), an Up's dot is clock.inc(actor)."""
-    ops = []
-    for i, (choice, inner_choice, key, inner_key, val) in enumerate(prims):
-        clock = [[actor, i]] if i > 0 else []
-        dot = [actor, i + 1]
-        if choice % 3 == 0:
-            if inner_choice % 3 == 0:
-                inner = {"up": {"dot": dot, "key": inner_key, "op": {"put": {"clock": clock, "val": val}}}}
-            elif inner_choice % 3 == 1:
-                inner = {"rm": {"clock": clock, "key": inner_key}}
-            else:
-                inner = "nop"
-            ops.append({"up": {"dot": dot, "key": key, "op": inner}})
-        elif choice % 3 == 1:
-            ops.append({"rm": {"clock": clock, "key": key}})
-        else:
-            ops.append("nop")
-    return actor, ops
-
-
-def rand_opvec(rng, actor=None):
-    """An arbitrary (u8, Vec<(u8, u8, u8, u8, u8)>) with keys drawn from a
-    small range (quickcheck's u8 keys rarely collide; a small range makes the
-    removes and concurrent updates meet)."""
-    n = rng.randrange(0, 12)
-    prims = [(rng.randrange(256), rng.randrange(256), rng.randrange(4), rng.randrange(4), rng.randrange(256))
-             for _ in range(n)]
-    return build_opvec(rng.randrange(256) if actor is None else actor, prims)
-
-
 def state(ops):
     m = mkr.nested_map()
     for op in ops:
         mkr.apply_raw(m, op)
     return m
-
-
-def distinct(rng, k):
-    acts = rng.sample(range(256), k)
-    return [rand_opvec(rng, a) for a in acts]
 
 
 N = 400

@@ -18,42 +18,7 @@ import pytest
 
 import map_kat_runner as mkr
 import map_slab
-from map_slab import crdts_ref
-
-SIZE = 100  # quickcheck's default size: u8 draws in [0, 100)
-
-
-def opvec(rng, actor, n_max=24, keys=SIZE, kind="mvreg"):
-    ops = []
-    for i in range(rng.randrange(0, n_max + 1)):
-        choice, inner, key, val = (rng.randrange(SIZE), rng.randrange(SIZE), rng.randrange(keys),
-                                   rng.randrange(SIZE))
-        clock = [(actor, i)] if i > 0 else []  # Dot{actor, 0}.into() is the empty clock
-        dot = (actor, i + 1)
-        if choice % 3 == 0:
-            ops.append(("up", dot, key, inner % 2 if kind == "orswot" else 0, val, clock))
-        elif choice % 3 == 1:
-            ops.append(("rm", None, key, None, None, clock))
-    return ops
-
-
-def apply_ops(be, m, ops, kind):
-    for op, dot, key, sub, val, clock in ops:
-        if op == "rm":
-            be.apply_rm(m, key, clock)
-        elif kind == "mvreg":
-            be.apply_up_put(m, dot, key, clock, val)
-        elif sub == 0:
-            be.apply_up_add(m, dot, key, val)
-        else:
-            _apply_up_orswot_rm(be, m, dot, key, val, clock)
-
-
-def _apply_up_orswot_rm(be, m, dot, key, member, clock):
-    if isinstance(be, mkr.OracleMapBackend):
-        m.apply_up_orswot(dot, key, 1, member, clock)
-    else:
-        m.apply_up(dot, key, lambda s: s.apply_rm(crdts_ref.VClock(clock), member))
+from map_exchange import SIZE, apply_ops, opvec  # the generator: shared with the op-exchange harness
 
 
 def build(rng, kind, keys, be):
