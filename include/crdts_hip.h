@@ -936,8 +936,14 @@ int crdt_map_map_truncate(crdt_ctx* ctx, const crdt_map_map_slab* self, const ui
  * output keeps the reference's order (self's survivors, then other's) and
  * zero-fills unused slots. cap <= 1024 per side (registers of <= 64 slots
  * per side whose rows fit 60 KB of LDS per wave take the fast kernel, the
- * rest a one-wave-per-pair kernel reading the rows from HBM); more survivors
- * than out_cap latch CRDT_ECAPACITY.                                        */
+ * rest a one-wave-per-pair kernel reading the rows from HBM; a wave's LDS is
+ * 8 (self_cap + other_cap) n_actors + self_cap other_cap + other_cap^2 +
+ * out_cap bytes, rounded up to 16, and a block holds as many waves, 4 at the
+ * most, as 60 KB allow); more survivors than out_cap latch CRDT_ECAPACITY, a
+ * count above its side's capacity CRDT_ENONCANON. Both are latched per
+ * object: that object's output is left unwritten and every other object is
+ * merged as usual. n_obj == 0 is CRDT_OK and launches nothing, null arrays
+ * included.                                                                 */
 int crdt_vclock_partial_cmp(crdt_ctx* ctx, const uint64_t* d_a, const uint64_t* d_b, size_t n,
                             uint32_t n_actors, int8_t* d_out, void* stream);
 int crdt_mvreg_merge(crdt_ctx* ctx, const uint32_t* d_self_n, const uint64_t* d_self_clk,

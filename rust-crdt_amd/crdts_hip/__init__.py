@@ -1020,18 +1020,15 @@ class Engine:
               "vclock_partial_cmp")
         return out
 
-    def mvreg_merge(self, self_slab, other_slab, n_actors, out_cap=None, stream=None, check_status=True):
+    def mvreg_merge(self, self_slab, other_slab, n_actors, out_cap=None, out=None, stream=None, check_status=True):
         """MVReg<u64, A>::merge (src/mvreg.rs:121-153) over slabs (n, clocks[n][cap][A], vals[n][cap])
-        of int32 / int64 device tensors; returns the output slab."""
-        torch = _torch()
+        of int32 / int64 device tensors; returns the output slab (`out`, or a new
+        one of out_cap slots, default: the two capacities' sum). Not in place."""
         sn, sc, sv = self_slab
         on, oc, ov = other_slab
         n_obj, scap, ocap = int(sn.numel()), int(sv.shape[1]), int(ov.shape[1])
-        cap = out_cap or scap + ocap
-        dev = sn.device
-        outn = torch.empty(n_obj, dtype=torch.int32, device=dev)
-        outc = torch.empty((n_obj, cap, n_actors), dtype=torch.int64, device=dev)
-        outv = torch.empty((n_obj, cap), dtype=torch.int64, device=dev)
+        cap = int(out[2].shape[1]) if out is not None else (out_cap or scap + ocap)
+        outn, outc, outv = self._mvreg_out(n_obj, cap, n_actors, sn.device, out)
         p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
         check(lib.crdt_mvreg_merge(self.ctx, p(sn), p(sc), p(sv), scap, p(on), p(oc), p(ov), ocap, p(outn), p(outc),
                                    p(outv), cap, n_obj, n_actors, self._stream(stream)), "mvreg_merge")

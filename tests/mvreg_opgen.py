@@ -1,6 +1,6 @@
 """Test helper: MVReg<u64, A> op lists (Op::Put, src/mvreg.rs:51-59) — a seeded
 generator, the rendering of oracle/crdts_ref.py::MVReg to the zero-filled slab
-of crdt_mvreg_merge / crdt_mvreg_apply, and the runner of the op-side KAT
+of crdt_mvreg_merge / crdt_mvreg_apply, and the runner of the KAT
 scripts (tests/golden/kat_mvreg_ops.json) over a backend.
 
 A register is a crdts_ref.MVReg; an op is (clock_pairs, val) with clock_pairs
@@ -162,6 +162,9 @@ class PyBackend:
     def apply(self, reg, op):
         reg.apply_put(crdts_ref.VClock(op[0]), op[1])
 
+    def merge(self, reg, other):
+        reg.merge(other)
+
     def read(self, reg):
         """(vals in order, add_clock pairs)."""
         return reg.read(), pairs_of(fold(reg))
@@ -174,8 +177,10 @@ def run_kat(case, be):
     """Runs one script; the reference's asserts are the script's assert steps.
     Steps: ["new", r] | ["set", op, r, actor, val] (reg.set(val,
     reg.read().derive_add_ctx(actor)): the register is not changed) |
-    ["put", op, pairs, val] | ["apply", r, op] | ["assert_read", r, vals, pairs]
-    | ["assert_eq", r1, r2] | ["assert_new", r]. Returns the applies made."""
+    ["put", op, pairs, val] | ["apply", r, op] | ["merge", r1, r2] (r1.merge(&r2))
+    | ["assert_read", r, vals, pairs] | ["assert_read_any", r, [vals, ...]] (the
+    values read are one of the lists) | ["assert_eq", r1, r2] | ["assert_new", r].
+    Returns the applies made."""
     regs, ops, applies = {}, {}, 0
     for st in case["steps"]:
         k = st[0]
@@ -191,6 +196,11 @@ def run_kat(case, be):
         elif k == "apply":
             be.apply(regs[st[1]], ops[st[2]])
             applies += 1
+        elif k == "merge":
+            be.merge(regs[st[1]], regs[st[2]])
+        elif k == "assert_read_any":
+            vals, _ = be.read(regs[st[1]])
+            assert list(vals) in st[2], (case["name"], st, vals)
         elif k == "assert_read":
             vals, clock = be.read(regs[st[1]])
             assert list(vals) == st[2], (case["name"], st, vals)

@@ -3,8 +3,9 @@
 crdt_mvreg_read_clock (:201-222), rust-crdt_amd/csrc/mvreg_apply.hip. Expected
 values come from oracle/crdts_ref.py::MVReg over the same op lists, rendered
 to the zero-filled slab (tests/mvreg_opgen.py); whole arrays are compared. The
-reference's op-side KATs and quickcheck properties (test/mvreg.rs) run with
-every apply / truncate / read on the kernels; the error contract is the
+reference's KATs and quickcheck properties (test/mvreg.rs) run with every
+apply / merge / truncate / read on the kernels (the merge itself is
+tests/test_gpu_mvreg_merge.py's); the error contract is the
 header's (include/crdts_hip.h)."""
 import ctypes as C
 import functools
@@ -77,8 +78,9 @@ def _reference(seed, n, A, cap, hi, min_ops, max_ops):
 # ------------------------------------------------------------------ 1. KATs
 class GpuBackend(mo.PyBackend):
     """A register is `reps` identical device registers; every apply is one
-    crdt_mvreg_apply launch over them, every read one crdt_mvreg_read_clock.
-    After every apply the state must be the Python restatement's."""
+    crdt_mvreg_apply launch over them, every merge one crdt_mvreg_merge, every
+    read one crdt_mvreg_read_clock. After every apply and merge the state must
+    be the Python restatement's."""
 
     A, CAP = 8, 4
 
@@ -93,6 +95,13 @@ class GpuBackend(mo.PyBackend):
                                    out=_patterned(self.reps, self.CAP, self.A))
         mo.PyBackend.apply(self, reg["py"], op)
         _assert_slab(_host(out), mo.slab([reg["py"]] * self.reps, self.CAP, self.A), what=str(op))
+        reg["slab"] = out
+
+    def merge(self, reg, other):
+        """One crdt_mvreg_merge launch over the copies (out_cap = CAP, below the capacities' sum)."""
+        out = self.eng.mvreg_merge(reg["slab"], other["slab"], self.A, out=_patterned(self.reps, self.CAP, self.A))
+        mo.PyBackend.merge(self, reg["py"], other["py"])
+        _assert_slab(_host(out), mo.slab([reg["py"]] * self.reps, self.CAP, self.A), what="merge")
         reg["slab"] = out
 
     def read(self, reg):
@@ -304,6 +313,40 @@ def test_prop_truncate(gpu):
     n, clk, val = _host(gpu.mvreg_truncate(slab, gpu.mvreg_read_clock(slab, PA), PA,
                                            out=_patterned(N_CASES, PCAP, PA)))
     assert (n == 0).all() and not clk.any() and not val.any()
+
+
+def _merge_dev(gpu, a, b):
+    """a.merge(&b) on the device, into a patterned slab of PCAP slots."""
+    return gpu.mvreg_merge(a, b, PA, out=_patterned(int(a[0].numel()), PCAP, PA))
+
+
+def test_prop_merge_idempotent(gpu):
+    slab, _ = _build_test_regs(gpu, _vectors(0x5A))
+    snap = _host(slab)
+    assert (snap[0] == 1).sum() > N_CASES // 2 and (snap[0] == 0).any()
+    again = _host(_merge_dev(gpu, slab, slab))
+    assert mo.setlike(*again) == mo.setlike(*snap)
+    _assert_slab(again, snap)
+
+
+def test_prop_merge_commutative(gpu):
+    v1, v2 = _vectors(0x5B, 0), _vectors(0x5C, 1)
+    assert sum(_not_compatible([a, b]) for a, b in zip(v1, v2)) == 0  # no case is discarded
+    (r1, _), (r2, _) = _build_test_regs(gpu, v1), _build_test_regs(gpu, v2)
+    a = _host(_merge_dev(gpu, r1, r2))
+    b = _host(_merge_dev(gpu, r2, r1))
+    assert mo.setlike(*a) == mo.setlike(*b)
+    assert (a[0] == 2).sum() > N_CASES // 2
+
+
+def test_prop_merge_associative(gpu):
+    v1, v2, v3 = _vectors(0x5D, 0), _vectors(0x5E, 1), _vectors(0x5F, 2)
+    assert sum(_not_compatible([a, b, c]) for a, b, c in zip(v1, v2, v3)) == 0  # no case is discarded
+    (r1, _), (r2, _), (r3, _) = (_build_test_regs(gpu, v) for v in (v1, v2, v3))
+    a = _host(_merge_dev(gpu, _merge_dev(gpu, r1, r2), r3))  # (r1 ^ r2) ^ r3
+    b = _host(_merge_dev(gpu, _merge_dev(gpu, r2, r3), r1))  # (r2 ^ r3) ^ r1
+    assert mo.setlike(*a) == mo.setlike(*b)
+    assert (a[0] == 3).sum() > N_CASES // 2
 
 
 def test_prop_op_idempotent(gpu):

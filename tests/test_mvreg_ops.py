@@ -58,12 +58,15 @@ def test_mvreg_op_kat_python(case):
 
 
 def test_mvreg_op_kat_names():
-    """The op-side tests within test/mvreg.rs:12-33, :60-79 and :105-118 (the
-    other two KATs of the file, :36-57 and :82-103, go through merge and are
-    tests/test_mvreg.py's)."""
+    """Every known-answer test of test/mvreg.rs (:12-118): the four op-side
+    ones, then the two that go through merge (:36-57 and :82-103; on the
+    oracle's slabs they are tests/test_mvreg.py's too)."""
     assert [c["name"] for c in KATS] == ["test_apply", "test_set_should_not_mutate_reg",
                                         "test_concurrent_update_with_same_value_dont_collapse_on_apply",
-                                        "test_op_commute_quickcheck1"]
+                                        "test_op_commute_quickcheck1",
+                                        "test_concurrent_update_with_same_value_dont_collapse_on_merge",
+                                        "test_multi_val"]
+    assert [sum(st[0] == "merge" for st in c["steps"]) for c in KATS] == [0, 0, 0, 0, 1, 1]
 
 
 @pytest.mark.parametrize("A,cap,hi", [(8, 4, 3), (16, 8, 2), (5, 16, 2), (1, 4, 3)])
