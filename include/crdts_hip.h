@@ -1107,6 +1107,87 @@ int crdt_orswot_to_bincode(crdt_ctx* ctx, const crdt_orswot_batch* batch, uint32
                            uint32_t actor_bytes, uint32_t member_bytes, uint8_t* d_out,
                            const uint64_t* d_out_off, size_t out_bytes, void* stream);
 
+/* ------------------------------------------------------------------------ *
+ * Ingest / egest of MVReg<V, A> (src/mvreg.rs:42-46) and Map<K, MVReg<V, A>,
+ * A> (src/map.rs:81-99; Entry :69-77): `to_binary` blobs (src/lib.rs:62-83)
+ * <-> the slabs of crdt_mvreg_merge / crdt_map_mvreg_merge. bincode 0.9 of
+ * the serde derives: a struct is its fields in order, a Vec / map / set a u64
+ * little-endian length and its elements, integers fixed-width little-endian:
+ *   VClock  u64 n | n x (A actor | u64 counter)           actors ascending
+ *   MVReg   u64 n_vals | n_vals x (VClock | V val)        Vec order (state)
+ *   Map     VClock clock
+ *           u64 n_entries | n_entries x (K key | VClock entry clock | MVReg)
+ *                                                         keys ascending
+ *           u64 n_def | n_def x (VClock | u64 n | n x K)  HashMap: clocks in
+ *                                        any order; BTreeSet: keys ascending
+ * A, K and V are unsigned integers of actor_bytes / key_bytes / val_bytes in
+ * {1, 2, 4, 8}, taken as the slab's actor ids, keys and values as they
+ * stand. Blob i is bytes [blob_off[i], blob_off[i] + blob_len[i]) of d_blobs
+ * (blob_bytes long; buffer and blobs at any alignment). All arrays are
+ * device arrays.
+ *
+ * Ingest = from_binary + the slab's canonical form: keys ascending and
+ * values in Vec order as in the blob, deferred clocks sorted into CLOCK ORDER
+ * (the one thing ingest reorders), their key sets ascending as in the blob.
+ * crdt_map_mvreg_from_bincode writes only the used slots of `out`;
+ * crdt_mvreg_from_bincode zero-fills every unused slot of its object.
+ * Latched per object (crdt_ctx_status; the other objects are unaffected, the
+ * object's row is unspecified; the MVReg slab's count of that object is 0):
+ *   CRDT_ENONCANON  a zero counter (a dense row cannot tell it from absent);
+ *                   an actor >= n_actors; actors, keys or deferred-set keys
+ *                   not strictly ascending; two equal deferred clocks; a blob
+ *                   that ends early or has trailing bytes; a length word
+ *                   larger than the bytes left could hold; a blob that is
+ *                   not inside d_blobs. Every length word is checked against
+ *                   the bytes left before anything it sizes is read: nothing
+ *                   outside a blob's aligned 16-byte lines within d_blobs is
+ *                   read.
+ *   CRDT_ECAPACITY  a well-formed blob with more keys, values per register,
+ *                   deferred clocks or deferred-set keys than out's
+ *                   capacities.
+ * Accepted, as the slab holds them: the empty map, an entry whose register
+ * has no values, an empty entry / value / deferred clock (an all-zero row).
+ *
+ * Egest = to_binary with the deferred HashMap in the slab's CLOCK ORDER (one
+ * of the orders the reference may produce; from_binary decodes an equal
+ * state), in two calls:
+ *   1) *_bincode_sizes: d_sizes[i] = blob bytes
+ *   2) the caller places the blobs (any byte offsets, e.g. an exclusive scan)
+ *   3) *_to_bincode writes blob i at d_out + d_out_off[i].
+ * Latched per object: CRDT_ENONCANON for a count above its capacity or a key,
+ * value or actor id that does not fit its byte width — that object's size is
+ * 0 and nothing of it is written; CRDT_ECAPACITY for a blob placed past
+ * out_bytes (not written).
+ *
+ * CRDT_EINVAL (before any device work): a null ctx or slab struct; a null
+ * array with n_obj > 0; a width outside {1, 2, 4, 8}; n_actors == 0 (Map:
+ * or > 128); ingest capacities outside the merges' per-side limits (Map:
+ * kcap <= 4096, mcap <= 128, dcap <= 64, scap <= 4096; MVReg: out_cap <=
+ * 1024), egest capacities outside those of a merge's output (twice them), a
+ * zero capacity; out_bytes below the smallest blob (Map 24, MVReg 8) with
+ * n_obj > 0. n_obj == 0 is CRDT_OK and launches nothing. CRDT_ENODEV without
+ * a device (crdt_ctx_create).                                              */
+int crdt_mvreg_from_bincode(crdt_ctx* ctx, const uint8_t* d_blobs, size_t blob_bytes,
+                            const uint64_t* d_blob_off, const uint64_t* d_blob_len, size_t n_obj,
+                            uint32_t actor_bytes, uint32_t val_bytes, uint32_t n_actors, uint32_t* d_out_n,
+                            uint64_t* d_out_clk, uint64_t* d_out_val, uint32_t out_cap, void* stream);
+int crdt_mvreg_bincode_sizes(crdt_ctx* ctx, const uint32_t* d_n, const uint64_t* d_clk, const uint64_t* d_val,
+                             uint32_t cap, size_t n_obj, uint32_t n_actors, uint32_t actor_bytes,
+                             uint32_t val_bytes, uint64_t* d_sizes, void* stream);
+int crdt_mvreg_to_bincode(crdt_ctx* ctx, const uint32_t* d_n, const uint64_t* d_clk, const uint64_t* d_val,
+                          uint32_t cap, size_t n_obj, uint32_t n_actors, uint32_t actor_bytes, uint32_t val_bytes,
+                          uint8_t* d_out, const uint64_t* d_out_off, size_t out_bytes, void* stream);
+int crdt_map_mvreg_from_bincode(crdt_ctx* ctx, const uint8_t* d_blobs, size_t blob_bytes,
+                                const uint64_t* d_blob_off, const uint64_t* d_blob_len, size_t n_obj,
+                                uint32_t actor_bytes, uint32_t key_bytes, uint32_t val_bytes, uint32_t n_actors,
+                                const crdt_map_mvreg_slab* out, void* stream);
+int crdt_map_mvreg_bincode_sizes(crdt_ctx* ctx, const crdt_map_mvreg_slab* slab, size_t n_obj, uint32_t n_actors,
+                                 uint32_t actor_bytes, uint32_t key_bytes, uint32_t val_bytes, uint64_t* d_sizes,
+                                 void* stream);
+int crdt_map_mvreg_to_bincode(crdt_ctx* ctx, const crdt_map_mvreg_slab* slab, size_t n_obj, uint32_t n_actors,
+                              uint32_t actor_bytes, uint32_t key_bytes, uint32_t val_bytes, uint8_t* d_out,
+                              const uint64_t* d_out_off, size_t out_bytes, void* stream);
+
 /* Dense synthetic counters: u64[n_obj][n_actors] rows for objects
  * [first_obj, first_obj+n_obj), counter U[0, 2^bits) with `pct_zero` % zeros. */
 int crdt_dense_generate(uint64_t seed, size_t first_obj, size_t n_obj, uint32_t n_actors,

@@ -1385,6 +1385,95 @@ class Engine:
             self.status(stream)
         return out, off, lens
 
+    def _placed(self, lens, stream):
+        """Exclusive scan of blob sizes -> (buffer, offsets): blobs packed back to back."""
+        torch = _torch()
+        n = int(lens.numel())
+        with torch.cuda.stream(stream) if stream is not None else _nullctx():
+            ends = torch.cumsum(lens, 0)
+            total = int(ends[-1].item()) if n else 0
+            off = ends - lens
+        return torch.empty(max(32, total), dtype=torch.uint8, device=lens.device), off
+
+    def mvreg_from_bincode(self, blobs, blob_off, blob_len, n_actors, actor_bytes, val_bytes, out_cap=None, out=None,
+                           stream=None, check_status=True):
+        """MVReg slabs (n, clocks[n][cap][A], vals[n][cap], as mvreg_merge takes
+        them) from `to_binary` blobs of MVReg<V, A> (src/mvreg.rs:42-46; src/lib.rs:
+        62-83). blobs: torch.uint8 device tensor; blob_off / blob_len: torch.int64
+        device tensors (u64). Returns `out`, or a new slab of out_cap slots
+        (required without `out`); every unused slot is zero-filled."""
+        n = int(blob_off.numel())
+        if out is None and not out_cap:
+            raise CrdtError(-1, "mvreg_from_bincode needs out or out_cap")
+        cap = int(out[2].shape[1]) if out is not None else int(out_cap)
+        outn, outc, outv = self._mvreg_out(n, cap, n_actors, blobs.device, out)
+        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        check(lib.crdt_mvreg_from_bincode(self.ctx, p(blobs), int(blobs.numel()), p(blob_off), p(blob_len), n,
+                                          actor_bytes, val_bytes, n_actors, p(outn), p(outc), p(outv), cap,
+                                          self._stream(stream)), "mvreg_from_bincode")
+        if check_status:
+            self.status(stream)
+        return outn, outc, outv
+
+    def mvreg_to_bincode(self, slab, n_actors, actor_bytes, val_bytes, stream=None, check_status=True):
+        """`to_binary` (src/lib.rs:62-64) of every register of an MVReg slab:
+        (blobs uint8, blob_off int64, blob_len int64) device tensors, the blobs
+        packed back to back (sizes, exclusive scan, write)."""
+        torch = _torch()
+        sn, sc, sv = slab
+        n, cap = int(sn.numel()), int(sv.shape[1])
+        st = self._stream(stream)
+        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        lens = torch.empty(n, dtype=torch.int64, device=sn.device)
+        check(lib.crdt_mvreg_bincode_sizes(self.ctx, p(sn), p(sc), p(sv), cap, n, n_actors, actor_bytes, val_bytes,
+                                           p(lens), st), "mvreg_bincode_sizes")
+        out, off = self._placed(lens, stream)
+        check(lib.crdt_mvreg_to_bincode(self.ctx, p(sn), p(sc), p(sv), cap, n, n_actors, actor_bytes, val_bytes,
+                                        p(out), p(off), int(out.numel()), st), "mvreg_to_bincode")
+        if check_status:
+            self.status(stream)
+        return out, off, lens
+
+    def map_mvreg_from_bincode(self, blobs, blob_off, blob_len, n_actors, actor_bytes, key_bytes, val_bytes,
+                               out_caps=None, out=None, stream=None, check_status=True):
+        """A MapSlab from `to_binary` blobs of Map<K, MVReg<V, A>, A> (src/map.rs:
+        81-99), in the slab's canonical form (deferred clocks in CLOCK ORDER).
+        Returns `out`, or a new slab of capacities out_caps = (kcap, mcap, dcap,
+        scap) (required without `out`). Only the used slots are written."""
+        n = int(blob_off.numel())
+        if out is None:
+            if out_caps is None:
+                raise CrdtError(-1, "map_mvreg_from_bincode needs out or out_caps")
+            out = MapSlab.alloc(n, n_actors, *out_caps, device=blobs.device)
+        r = out.cstruct()
+        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        check(lib.crdt_map_mvreg_from_bincode(self.ctx, p(blobs), int(blobs.numel()), p(blob_off), p(blob_len), n,
+                                              actor_bytes, key_bytes, val_bytes, n_actors, C.byref(r),
+                                              self._stream(stream)), "map_mvreg_from_bincode")
+        if check_status:
+            self.status(stream)
+        return out
+
+    def map_mvreg_to_bincode(self, S: "MapSlab", n_actors, actor_bytes, key_bytes, val_bytes, stream=None,
+                             check_status=True):
+        """`to_binary` of every map of a MapSlab, the deferred clocks in the
+        slab's CLOCK ORDER: (blobs uint8, blob_off int64, blob_len int64) device
+        tensors, the blobs packed back to back (sizes, exclusive scan, write)."""
+        torch = _torch()
+        n = int(S.a["n_keys"].shape[0])
+        st = self._stream(stream)
+        s = S.cstruct()
+        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        lens = torch.empty(n, dtype=torch.int64, device=S.a["clock"].device)
+        check(lib.crdt_map_mvreg_bincode_sizes(self.ctx, C.byref(s), n, n_actors, actor_bytes, key_bytes, val_bytes,
+                                               p(lens), st), "map_mvreg_bincode_sizes")
+        out, off = self._placed(lens, stream)
+        check(lib.crdt_map_mvreg_to_bincode(self.ctx, C.byref(s), n, n_actors, actor_bytes, key_bytes, val_bytes,
+                                            p(out), p(off), int(out.numel()), st), "map_mvreg_to_bincode")
+        if check_status:
+            self.status(stream)
+        return out, off, lens
+
     def orswot_truncate(self, B: OrswotBatch, clocks: "ClockBatch", out: "OrswotBatch | None" = None, stream=None,
                         check_status=True):
         """out[i] = B[i] after Causal::truncate(&clocks[i]) (src/orswot.rs:159-172),

@@ -82,6 +82,8 @@ EXPORTS = [
     "crdt_mvreg_apply", "crdt_mvreg_truncate", "crdt_mvreg_read_clock",
     "crdt_map_mvreg_truncate", "crdt_map_orswot_truncate", "crdt_map_map_truncate_scratch_bytes",
     "crdt_map_map_truncate",
+    "crdt_mvreg_from_bincode", "crdt_mvreg_bincode_sizes", "crdt_mvreg_to_bincode",
+    "crdt_map_mvreg_from_bincode", "crdt_map_mvreg_bincode_sizes", "crdt_map_mvreg_to_bincode",
 ]
 
 CRDT_COMM_ID_BYTES = 128
@@ -271,6 +273,12 @@ def _load():
         "crdt_map_orswot_truncate": (I, [P, C.POINTER(MapOrswotSlabC), P, C.POINTER(MapOrswotSlabC), SZ, U32, P]),
         "crdt_map_map_truncate_scratch_bytes": (SZ, [C.POINTER(MapMapSlabC), SZ, U32]),
         "crdt_map_map_truncate": (I, [P, C.POINTER(MapMapSlabC), P, C.POINTER(MapMapSlabC), SZ, U32, P, SZ, P]),
+        "crdt_mvreg_from_bincode": (I, [P, P, SZ, P, P, SZ, U32, U32, U32, P, P, P, U32, P]),
+        "crdt_mvreg_bincode_sizes": (I, [P, P, P, P, U32, SZ, U32, U32, U32, P, P]),
+        "crdt_mvreg_to_bincode": (I, [P, P, P, P, U32, SZ, U32, U32, U32, P, P, SZ, P]),
+        "crdt_map_mvreg_from_bincode": (I, [P, P, SZ, P, P, SZ, U32, U32, U32, U32, C.POINTER(MapSlabC), P]),
+        "crdt_map_mvreg_bincode_sizes": (I, [P, C.POINTER(MapSlabC), SZ, U32, U32, U32, U32, P, P]),
+        "crdt_map_mvreg_to_bincode": (I, [P, C.POINTER(MapSlabC), SZ, U32, U32, U32, U32, P, P, SZ, P]),
         "crdt_comm_unique_id": (I, [P]),
         "crdt_comm_init": (I, [P, P, I, I]),
         "crdt_comm_destroy": (I, [P]),

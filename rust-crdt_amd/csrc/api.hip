@@ -855,4 +855,89 @@ int crdt_map_map_truncate(crdt_ctx* ctx, const crdt_map_map_slab* self, const ui
                                  ctx->d_ctl, S(stream));
 }
 
+// ------------------------------------------- bincode codec, MVReg and Map<u64, MVReg>
+// egest reads any slab a merge or an apply can leave: the sums of the merge's per-side limits
+static bool map_mvreg_egest_caps_ok(const crdt_map_mvreg_slab* x) {
+  return x->kcap && x->kcap <= 8192 && x->mcap && x->mcap <= 256 && x->dcap && x->dcap <= 128 && x->scap &&
+         x->scap <= 8192;
+}
+
+int crdt_mvreg_from_bincode(crdt_ctx* ctx, const uint8_t* d_blobs, size_t blob_bytes, const uint64_t* d_blob_off,
+                            const uint64_t* d_blob_len, size_t n_obj, uint32_t actor_bytes, uint32_t val_bytes,
+                            uint32_t n_actors, uint32_t* d_out_n, uint64_t* d_out_clk, uint64_t* d_out_val,
+                            uint32_t out_cap, void* stream) {
+  if (!ctx || n_actors == 0 || !bc_width_ok(actor_bytes) || !bc_width_ok(val_bytes) || out_cap == 0 || out_cap > 1024)
+    return CRDT_EINVAL;
+  if (n_obj && (!d_blobs || !d_blob_off || !d_blob_len || !d_out_n || !d_out_clk || !d_out_val)) return CRDT_EINVAL;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_mvreg_bincode_ingest(d_blobs, blob_bytes, d_blob_off, d_blob_len, n_obj, actor_bytes, val_bytes,
+                                     n_actors, d_out_n, d_out_clk, d_out_val, out_cap, ctx->d_status, S(stream));
+}
+
+int crdt_mvreg_bincode_sizes(crdt_ctx* ctx, const uint32_t* d_n, const uint64_t* d_clk, const uint64_t* d_val,
+                             uint32_t cap, size_t n_obj, uint32_t n_actors, uint32_t actor_bytes, uint32_t val_bytes,
+                             uint64_t* d_sizes, void* stream) {
+  if (!ctx || n_actors == 0 || !bc_width_ok(actor_bytes) || !bc_width_ok(val_bytes) || cap == 0 || cap > 2048)
+    return CRDT_EINVAL;
+  if (n_obj && (!d_n || !d_clk || !d_val || !d_sizes)) return CRDT_EINVAL;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_mvreg_bincode_egest(d_n, d_clk, d_val, cap, n_obj, n_actors, actor_bytes, val_bytes, d_sizes, nullptr,
+                                    nullptr, 0, ctx->d_status, S(stream));
+}
+
+int crdt_mvreg_to_bincode(crdt_ctx* ctx, const uint32_t* d_n, const uint64_t* d_clk, const uint64_t* d_val,
+                          uint32_t cap, size_t n_obj, uint32_t n_actors, uint32_t actor_bytes, uint32_t val_bytes,
+                          uint8_t* d_out, const uint64_t* d_out_off, size_t out_bytes, void* stream) {
+  if (!ctx || n_actors == 0 || !bc_width_ok(actor_bytes) || !bc_width_ok(val_bytes) || cap == 0 || cap > 2048)
+    return CRDT_EINVAL;
+  if (n_obj && (!d_n || !d_clk || !d_val || !d_out || !d_out_off)) return CRDT_EINVAL;
+  if (n_obj && out_bytes < 8u) return CRDT_EINVAL;  // the smallest blob (an empty register) is 8 bytes
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_mvreg_bincode_egest(d_n, d_clk, d_val, cap, n_obj, n_actors, actor_bytes, val_bytes, nullptr, d_out,
+                                    d_out_off, out_bytes, ctx->d_status, S(stream));
+}
+
+int crdt_map_mvreg_from_bincode(crdt_ctx* ctx, const uint8_t* d_blobs, size_t blob_bytes, const uint64_t* d_blob_off,
+                                const uint64_t* d_blob_len, size_t n_obj, uint32_t actor_bytes, uint32_t key_bytes,
+                                uint32_t val_bytes, uint32_t n_actors, const crdt_map_mvreg_slab* out, void* stream) {
+  if (!ctx || !out || n_actors == 0 || n_actors > 128 || !bc_width_ok(actor_bytes) || !bc_width_ok(key_bytes) ||
+      !bc_width_ok(val_bytes) || !map_mvreg_caps_ok(out))
+    return CRDT_EINVAL;
+  if (n_obj && (!d_blobs || !d_blob_off || !d_blob_len || !map_mvreg_ptrs_ok(out))) return CRDT_EINVAL;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_map_bincode_ingest(d_blobs, blob_bytes, d_blob_off, d_blob_len, n_obj, actor_bytes, key_bytes,
+                                   val_bytes, n_actors, *out, ctx->d_status, S(stream));
+}
+
+int crdt_map_mvreg_bincode_sizes(crdt_ctx* ctx, const crdt_map_mvreg_slab* slab, size_t n_obj, uint32_t n_actors,
+                                 uint32_t actor_bytes, uint32_t key_bytes, uint32_t val_bytes, uint64_t* d_sizes,
+                                 void* stream) {
+  if (!ctx || !slab || n_actors == 0 || n_actors > 128 || !bc_width_ok(actor_bytes) || !bc_width_ok(key_bytes) ||
+      !bc_width_ok(val_bytes) || !map_mvreg_egest_caps_ok(slab))
+    return CRDT_EINVAL;
+  if (n_obj && (!map_mvreg_ptrs_ok(slab) || !d_sizes)) return CRDT_EINVAL;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_map_bincode_egest(*slab, n_obj, n_actors, actor_bytes, key_bytes, val_bytes, d_sizes, nullptr, nullptr,
+                                  0, ctx->d_status, S(stream));
+}
+
+int crdt_map_mvreg_to_bincode(crdt_ctx* ctx, const crdt_map_mvreg_slab* slab, size_t n_obj, uint32_t n_actors,
+                              uint32_t actor_bytes, uint32_t key_bytes, uint32_t val_bytes, uint8_t* d_out,
+                              const uint64_t* d_out_off, size_t out_bytes, void* stream) {
+  if (!ctx || !slab || n_actors == 0 || n_actors > 128 || !bc_width_ok(actor_bytes) || !bc_width_ok(key_bytes) ||
+      !bc_width_ok(val_bytes) || !map_mvreg_egest_caps_ok(slab))
+    return CRDT_EINVAL;
+  if (n_obj && (!map_mvreg_ptrs_ok(slab) || !d_out || !d_out_off)) return CRDT_EINVAL;
+  if (n_obj && out_bytes < 24u) return CRDT_EINVAL;  // the smallest blob (the empty map) is 24 bytes
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_map_bincode_egest(*slab, n_obj, n_actors, actor_bytes, key_bytes, val_bytes, nullptr, d_out, d_out_off,
+                                  out_bytes, ctx->d_status, S(stream));
+}
+
 }  // extern "C"

@@ -137,4 +137,20 @@ int launch_map_map_truncate(const crdt_map_map_slab& S, const uint64_t* clk, con
                             uint64_t n_obj, uint32_t A, uint8_t* scratch, int* status, uint32_t* ctl,
                             hipStream_t stream);
 
+// bincode codec of MVReg / Map<u64, MVReg> over their slabs (map_bincode.hip);
+// widths in {1, 2, 4, 8}, capacities within the ABI limits (api.hip). Egest:
+// out == nullptr is the sizes pass.
+int launch_map_bincode_ingest(const uint8_t* blobs, uint64_t blob_bytes, const uint64_t* boff, const uint64_t* blen,
+                              uint64_t n_obj, uint32_t wa, uint32_t wk, uint32_t wv, uint32_t A,
+                              const crdt_map_mvreg_slab& R, int* status, hipStream_t stream);
+int launch_mvreg_bincode_ingest(const uint8_t* blobs, uint64_t blob_bytes, const uint64_t* boff, const uint64_t* blen,
+                                uint64_t n_obj, uint32_t wa, uint32_t wv, uint32_t A, uint32_t* outn, uint64_t* outclk,
+                                uint64_t* outval, uint32_t cap, int* status, hipStream_t stream);
+int launch_map_bincode_egest(const crdt_map_mvreg_slab& S, uint64_t n_obj, uint32_t A, uint32_t wa, uint32_t wk,
+                             uint32_t wv, uint64_t* sizes, uint8_t* out, const uint64_t* ooff, uint64_t out_bytes,
+                             int* status, hipStream_t stream);
+int launch_mvreg_bincode_egest(const uint32_t* sn, const uint64_t* sclk, const uint64_t* sval, uint32_t cap,
+                               uint64_t n_obj, uint32_t A, uint32_t wa, uint32_t wv, uint64_t* sizes, uint8_t* out,
+                               const uint64_t* ooff, uint64_t out_bytes, int* status, hipStream_t stream);
+
 }  // namespace crdts_hip
