@@ -1188,6 +1188,70 @@ int crdt_map_mvreg_to_bincode(crdt_ctx* ctx, const crdt_map_mvreg_slab* slab, si
                               uint32_t actor_bytes, uint32_t key_bytes, uint32_t val_bytes, uint8_t* d_out,
                               const uint64_t* d_out_off, size_t out_bytes, void* stream);
 
+/* ------------------------------------------------------------------------ *
+ * Ingest / egest of the two Map types whose values are containers:
+ * Map<K, Orswot<M, A>, A> <-> crdt_map_orswot_slab and Map<K, Map<K2,
+ * MVReg<V, A>, A>, A> (the reference's TestMap, test/map.rs:4-8) <->
+ * crdt_map_map_slab. The format is the one above, with
+ *   Orswot  VClock clock                                  src/orswot.rs:26-30
+ *           u64 n_mem | n_mem x (M member | VClock)       HashMap: any order
+ *           u64 n_def | n_def x (VClock | u64 n | n x M)  HashMap of HashSet:
+ *                                  clocks in any order, members in any order
+ *   Map<K, V>  as above with an entry = K key | VClock entry clock | V, where
+ *           V = Orswot<M, A> (crdt_map_orswot_*) or V = Map<K2, MVReg<V2, A>,
+ *           A>, the Map form again (crdt_map_map_*).
+ * Widths (actor, key, member / inner key, value bytes) are in {1, 2, 4, 8};
+ * blobs, offsets, lengths, the stream and the two-call egest are as for
+ * crdt_map_mvreg_*. Inner map k of object i is row i * kcap + k of out->inner.
+ *
+ * Ingest = from_binary + the slab's canonical form; only the used slots of
+ * `out` are written. Map<K, Orswot>: every nested set's members are sorted
+ * ascending (each member clock row follows its member), its deferred clocks
+ * put into CLOCK ORDER, each deferred member set sorted ascending, and the
+ * map's deferred clocks put into CLOCK ORDER. The nested map: the outer and
+ * the inner deferred clocks are put into CLOCK ORDER; everything else is a
+ * BTree (checked strictly ascending) or a Vec (order kept). Accepted: the
+ * empty map, an empty nested set or inner map, an empty clock anywhere (an
+ * empty member clock is an all-zero row), a register without values.
+ * Latched per object, the other objects unaffected:
+ *   CRDT_ENONCANON  as for crdt_map_mvreg_from_bincode, and: two equal
+ *                   members in one nested set or in one deferred member set.
+ *   CRDT_ECAPACITY  a well-formed blob with more of anything than out's
+ *                   capacities.
+ * Egest writes every unordered container in the slab's order; errors as for
+ * crdt_map_mvreg_to_bincode (a count above its capacity, or a key, member,
+ * value or actor id that does not fit its width: CRDT_ENONCANON, size 0,
+ * nothing written; a blob placed past out_bytes: CRDT_ECAPACITY).
+ *
+ * CRDT_EINVAL (before any device work): a null ctx or slab struct; a null
+ * array with n_obj > 0; a width outside {1, 2, 4, 8}; n_actors == 0 or > 128;
+ * a zero capacity; ingest capacities outside the merges' static per-side
+ * limits (Map<K, Orswot>: kcap <= 4096, mcap, vdcap, vscap, dcap <= 256, scap
+ * <= 4096 — the merge's 64 KB workspace rule is the merge's own and is not
+ * applied; nested map: outer kcap <= 4096, dcap <= 64, scap <= 4096, inner
+ * as crdt_map_mvreg_merge's); egest capacities above twice those; out_bytes
+ * below 24 with n_obj > 0. n_obj == 0 is CRDT_OK and launches nothing.      */
+int crdt_map_orswot_from_bincode(crdt_ctx* ctx, const uint8_t* d_blobs, size_t blob_bytes,
+                                 const uint64_t* d_blob_off, const uint64_t* d_blob_len, size_t n_obj,
+                                 uint32_t actor_bytes, uint32_t key_bytes, uint32_t member_bytes, uint32_t n_actors,
+                                 const crdt_map_orswot_slab* out, void* stream);
+int crdt_map_orswot_bincode_sizes(crdt_ctx* ctx, const crdt_map_orswot_slab* slab, size_t n_obj, uint32_t n_actors,
+                                  uint32_t actor_bytes, uint32_t key_bytes, uint32_t member_bytes, uint64_t* d_sizes,
+                                  void* stream);
+int crdt_map_orswot_to_bincode(crdt_ctx* ctx, const crdt_map_orswot_slab* slab, size_t n_obj, uint32_t n_actors,
+                               uint32_t actor_bytes, uint32_t key_bytes, uint32_t member_bytes, uint8_t* d_out,
+                               const uint64_t* d_out_off, size_t out_bytes, void* stream);
+int crdt_map_map_from_bincode(crdt_ctx* ctx, const uint8_t* d_blobs, size_t blob_bytes, const uint64_t* d_blob_off,
+                              const uint64_t* d_blob_len, size_t n_obj, uint32_t actor_bytes, uint32_t key_bytes,
+                              uint32_t inner_key_bytes, uint32_t val_bytes, uint32_t n_actors,
+                              const crdt_map_map_slab* out, void* stream);
+int crdt_map_map_bincode_sizes(crdt_ctx* ctx, const crdt_map_map_slab* slab, size_t n_obj, uint32_t n_actors,
+                               uint32_t actor_bytes, uint32_t key_bytes, uint32_t inner_key_bytes, uint32_t val_bytes,
+                               uint64_t* d_sizes, void* stream);
+int crdt_map_map_to_bincode(crdt_ctx* ctx, const crdt_map_map_slab* slab, size_t n_obj, uint32_t n_actors,
+                            uint32_t actor_bytes, uint32_t key_bytes, uint32_t inner_key_bytes, uint32_t val_bytes,
+                            uint8_t* d_out, const uint64_t* d_out_off, size_t out_bytes, void* stream);
+
 /* Dense synthetic counters: u64[n_obj][n_actors] rows for objects
  * [first_obj, first_obj+n_obj), counter U[0, 2^bits) with `pct_zero` % zeros. */
 int crdt_dense_generate(uint64_t seed, size_t first_obj, size_t n_obj, uint32_t n_actors,

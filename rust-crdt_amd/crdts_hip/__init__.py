@@ -1474,6 +1474,81 @@ class Engine:
             self.status(stream)
         return out, off, lens
 
+    def _nested_to_bincode(self, name, S, n_actors, widths, stream, check_status):
+        torch = _torch()
+        n = int(S.a["n_keys"].shape[0])
+        st = self._stream(stream)
+        s = S.cstruct()
+        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        lens = torch.empty(n, dtype=torch.int64, device=S.a["clock"].device)
+        check(getattr(lib, f"crdt_{name}_bincode_sizes")(self.ctx, C.byref(s), n, n_actors, *widths, p(lens), st),
+              f"{name}_bincode_sizes")
+        out, off = self._placed(lens, stream)
+        check(getattr(lib, f"crdt_{name}_to_bincode")(self.ctx, C.byref(s), n, n_actors, *widths, p(out), p(off),
+                                                      int(out.numel()), st), f"{name}_to_bincode")
+        if check_status:
+            self.status(stream)
+        return out, off, lens
+
+    def map_orswot_from_bincode(self, blobs, blob_off, blob_len, n_actors, actor_bytes, key_bytes, member_bytes,
+                                out_caps=None, out=None, stream=None, check_status=True):
+        """A MapOrswotSlab from `to_binary` blobs of Map<K, Orswot<M, A>, A>, in
+        the slab's canonical form: members and deferred member sets sorted
+        ascending, nested and map deferred clocks in CLOCK ORDER. Returns `out`,
+        or a new slab of capacities out_caps = dict(kcap, mcap, vdcap, vscap,
+        dcap, scap) (required without `out`). Only the used slots are written."""
+        n = int(blob_off.numel())
+        if out is None:
+            if out_caps is None:
+                raise CrdtError(-1, "map_orswot_from_bincode needs out or out_caps")
+            out = MapOrswotSlab.alloc(n, n_actors, device=blobs.device, **out_caps)
+        r = out.cstruct()
+        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        check(lib.crdt_map_orswot_from_bincode(self.ctx, p(blobs), int(blobs.numel()), p(blob_off), p(blob_len), n,
+                                               actor_bytes, key_bytes, member_bytes, n_actors, C.byref(r),
+                                               self._stream(stream)), "map_orswot_from_bincode")
+        if check_status:
+            self.status(stream)
+        return out
+
+    def map_orswot_to_bincode(self, S: "MapOrswotSlab", n_actors, actor_bytes, key_bytes, member_bytes, stream=None,
+                              check_status=True):
+        """`to_binary` of every map of a MapOrswotSlab, every unordered
+        container in the slab's order: (blobs uint8, blob_off int64, blob_len
+        int64) device tensors, the blobs packed back to back (sizes, exclusive
+        scan, write)."""
+        return self._nested_to_bincode("map_orswot", S, n_actors, (actor_bytes, key_bytes, member_bytes), stream,
+                                       check_status)
+
+    def map_map_from_bincode(self, blobs, blob_off, blob_len, n_actors, actor_bytes, key_bytes, inner_key_bytes,
+                             val_bytes, out_caps=None, out=None, stream=None, check_status=True):
+        """A MapMapSlab from `to_binary` blobs of Map<K, Map<K2, MVReg<V, A>, A>,
+        A> (the reference's TestMap), outer and inner deferred clocks in CLOCK
+        ORDER. Returns `out`, or a new slab of capacities out_caps = (kcap, dcap,
+        scap, inner_caps) with inner_caps = (kcap, mcap, dcap, scap) (required
+        without `out`). Only the used slots are written."""
+        n = int(blob_off.numel())
+        if out is None:
+            if out_caps is None:
+                raise CrdtError(-1, "map_map_from_bincode needs out or out_caps")
+            out = MapMapSlab.alloc(n, n_actors, *out_caps, device=blobs.device)
+        r = out.cstruct()
+        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        check(lib.crdt_map_map_from_bincode(self.ctx, p(blobs), int(blobs.numel()), p(blob_off), p(blob_len), n,
+                                            actor_bytes, key_bytes, inner_key_bytes, val_bytes, n_actors, C.byref(r),
+                                            self._stream(stream)), "map_map_from_bincode")
+        if check_status:
+            self.status(stream)
+        return out
+
+    def map_map_to_bincode(self, S: "MapMapSlab", n_actors, actor_bytes, key_bytes, inner_key_bytes, val_bytes,
+                           stream=None, check_status=True):
+        """`to_binary` of every map of a MapMapSlab, deferred clocks in the
+        slab's CLOCK ORDER: (blobs uint8, blob_off int64, blob_len int64) device
+        tensors, the blobs packed back to back (sizes, exclusive scan, write)."""
+        return self._nested_to_bincode("map_map", S, n_actors, (actor_bytes, key_bytes, inner_key_bytes, val_bytes),
+                                       stream, check_status)
+
     def orswot_truncate(self, B: OrswotBatch, clocks: "ClockBatch", out: "OrswotBatch | None" = None, stream=None,
                         check_status=True):
         """out[i] = B[i] after Causal::truncate(&clocks[i]) (src/orswot.rs:159-172),

@@ -84,6 +84,8 @@ EXPORTS = [
     "crdt_map_map_truncate",
     "crdt_mvreg_from_bincode", "crdt_mvreg_bincode_sizes", "crdt_mvreg_to_bincode",
     "crdt_map_mvreg_from_bincode", "crdt_map_mvreg_bincode_sizes", "crdt_map_mvreg_to_bincode",
+    "crdt_map_orswot_from_bincode", "crdt_map_orswot_bincode_sizes", "crdt_map_orswot_to_bincode",
+    "crdt_map_map_from_bincode", "crdt_map_map_bincode_sizes", "crdt_map_map_to_bincode",
 ]
 
 CRDT_COMM_ID_BYTES = 128
@@ -279,6 +281,12 @@ def _load():
         "crdt_map_mvreg_from_bincode": (I, [P, P, SZ, P, P, SZ, U32, U32, U32, U32, C.POINTER(MapSlabC), P]),
         "crdt_map_mvreg_bincode_sizes": (I, [P, C.POINTER(MapSlabC), SZ, U32, U32, U32, U32, P, P]),
         "crdt_map_mvreg_to_bincode": (I, [P, C.POINTER(MapSlabC), SZ, U32, U32, U32, U32, P, P, SZ, P]),
+        "crdt_map_orswot_from_bincode": (I, [P, P, SZ, P, P, SZ, U32, U32, U32, U32, C.POINTER(MapOrswotSlabC), P]),
+        "crdt_map_orswot_bincode_sizes": (I, [P, C.POINTER(MapOrswotSlabC), SZ, U32, U32, U32, U32, P, P]),
+        "crdt_map_orswot_to_bincode": (I, [P, C.POINTER(MapOrswotSlabC), SZ, U32, U32, U32, U32, P, P, SZ, P]),
+        "crdt_map_map_from_bincode": (I, [P, P, SZ, P, P, SZ, U32, U32, U32, U32, U32, C.POINTER(MapMapSlabC), P]),
+        "crdt_map_map_bincode_sizes": (I, [P, C.POINTER(MapMapSlabC), SZ, U32, U32, U32, U32, U32, P, P]),
+        "crdt_map_map_to_bincode": (I, [P, C.POINTER(MapMapSlabC), SZ, U32, U32, U32, U32, U32, P, P, SZ, P]),
         "crdt_comm_unique_id": (I, [P]),
         "crdt_comm_init": (I, [P, P, I, I]),
         "crdt_comm_destroy": (I, [P]),

@@ -940,4 +940,102 @@ int crdt_map_mvreg_to_bincode(crdt_ctx* ctx, const crdt_map_mvreg_slab* slab, si
                                   out_bytes, ctx->d_status, S(stream));
 }
 
+// ------------------------------------ bincode codec, Map<u64, Orswot> and the nested map
+// ingest: the merges' static per-side limits (the Map<u64, Orswot> merge's
+// workspace rule is the merge's own); egest: twice them, a merge's or an apply's output
+static bool map_orswot_codec_caps_ok(const crdt_map_orswot_slab* x, uint32_t f) {
+  return x->kcap && x->kcap <= 4096u * f && x->mcap && x->mcap <= 256u * f && x->vdcap && x->vdcap <= 256u * f &&
+         x->vscap && x->vscap <= 256u * f && x->dcap && x->dcap <= 256u * f && x->scap && x->scap <= 4096u * f;
+}
+static bool map_map_codec_caps_ok(const crdt_map_map_slab* x, bool egest) {
+  const uint32_t f = egest ? 2u : 1u;
+  return x->kcap && x->kcap <= 4096u * f && x->dcap && x->dcap <= 64u * f && x->scap && x->scap <= 4096u * f &&
+         (egest ? map_mvreg_egest_caps_ok(&x->inner) : map_mvreg_caps_ok(&x->inner));
+}
+static bool bc_widths_ok(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
+  return bc_width_ok(a) && bc_width_ok(b) && bc_width_ok(c) && bc_width_ok(d);
+}
+
+int crdt_map_orswot_from_bincode(crdt_ctx* ctx, const uint8_t* d_blobs, size_t blob_bytes,
+                                 const uint64_t* d_blob_off, const uint64_t* d_blob_len, size_t n_obj,
+                                 uint32_t actor_bytes, uint32_t key_bytes, uint32_t member_bytes, uint32_t n_actors,
+                                 const crdt_map_orswot_slab* out, void* stream) {
+  if (!ctx || !out || n_actors == 0 || n_actors > 128 || !bc_widths_ok(actor_bytes, key_bytes, member_bytes, 1u) ||
+      !map_orswot_codec_caps_ok(out, 1u))
+    return CRDT_EINVAL;
+  if (n_obj && (!d_blobs || !d_blob_off || !d_blob_len || !map_orswot_ptrs_ok(out))) return CRDT_EINVAL;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_map_orswot_bincode_ingest(d_blobs, blob_bytes, d_blob_off, d_blob_len, n_obj, actor_bytes, key_bytes,
+                                          member_bytes, n_actors, *out, ctx->d_status, S(stream));
+}
+
+int crdt_map_orswot_bincode_sizes(crdt_ctx* ctx, const crdt_map_orswot_slab* slab, size_t n_obj, uint32_t n_actors,
+                                  uint32_t actor_bytes, uint32_t key_bytes, uint32_t member_bytes, uint64_t* d_sizes,
+                                  void* stream) {
+  if (!ctx || !slab || n_actors == 0 || n_actors > 128 || !bc_widths_ok(actor_bytes, key_bytes, member_bytes, 1u) ||
+      !map_orswot_codec_caps_ok(slab, 2u))
+    return CRDT_EINVAL;
+  if (n_obj && (!map_orswot_ptrs_ok(slab) || !d_sizes)) return CRDT_EINVAL;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_map_orswot_bincode_egest(*slab, n_obj, n_actors, actor_bytes, key_bytes, member_bytes, d_sizes,
+                                         nullptr, nullptr, 0, ctx->d_status, S(stream));
+}
+
+int crdt_map_orswot_to_bincode(crdt_ctx* ctx, const crdt_map_orswot_slab* slab, size_t n_obj, uint32_t n_actors,
+                               uint32_t actor_bytes, uint32_t key_bytes, uint32_t member_bytes, uint8_t* d_out,
+                               const uint64_t* d_out_off, size_t out_bytes, void* stream) {
+  if (!ctx || !slab || n_actors == 0 || n_actors > 128 || !bc_widths_ok(actor_bytes, key_bytes, member_bytes, 1u) ||
+      !map_orswot_codec_caps_ok(slab, 2u))
+    return CRDT_EINVAL;
+  if (n_obj && (!map_orswot_ptrs_ok(slab) || !d_out || !d_out_off)) return CRDT_EINVAL;
+  if (n_obj && out_bytes < 24u) return CRDT_EINVAL;  // the smallest blob (the empty map) is 24 bytes
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_map_orswot_bincode_egest(*slab, n_obj, n_actors, actor_bytes, key_bytes, member_bytes, nullptr, d_out,
+                                         d_out_off, out_bytes, ctx->d_status, S(stream));
+}
+
+int crdt_map_map_from_bincode(crdt_ctx* ctx, const uint8_t* d_blobs, size_t blob_bytes, const uint64_t* d_blob_off,
+                              const uint64_t* d_blob_len, size_t n_obj, uint32_t actor_bytes, uint32_t key_bytes,
+                              uint32_t inner_key_bytes, uint32_t val_bytes, uint32_t n_actors,
+                              const crdt_map_map_slab* out, void* stream) {
+  if (!ctx || !out || n_actors == 0 || n_actors > 128 ||
+      !bc_widths_ok(actor_bytes, key_bytes, inner_key_bytes, val_bytes) || !map_map_codec_caps_ok(out, false))
+    return CRDT_EINVAL;
+  if (n_obj && (!d_blobs || !d_blob_off || !d_blob_len || !map_map_ptrs_ok(out))) return CRDT_EINVAL;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_map_map_bincode_ingest(d_blobs, blob_bytes, d_blob_off, d_blob_len, n_obj, actor_bytes, key_bytes,
+                                       inner_key_bytes, val_bytes, n_actors, *out, ctx->d_status, S(stream));
+}
+
+int crdt_map_map_bincode_sizes(crdt_ctx* ctx, const crdt_map_map_slab* slab, size_t n_obj, uint32_t n_actors,
+                               uint32_t actor_bytes, uint32_t key_bytes, uint32_t inner_key_bytes, uint32_t val_bytes,
+                               uint64_t* d_sizes, void* stream) {
+  if (!ctx || !slab || n_actors == 0 || n_actors > 128 ||
+      !bc_widths_ok(actor_bytes, key_bytes, inner_key_bytes, val_bytes) || !map_map_codec_caps_ok(slab, true))
+    return CRDT_EINVAL;
+  if (n_obj && (!map_map_ptrs_ok(slab) || !d_sizes)) return CRDT_EINVAL;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_map_map_bincode_egest(*slab, n_obj, n_actors, actor_bytes, key_bytes, inner_key_bytes, val_bytes,
+                                      d_sizes, nullptr, nullptr, 0, ctx->d_status, S(stream));
+}
+
+int crdt_map_map_to_bincode(crdt_ctx* ctx, const crdt_map_map_slab* slab, size_t n_obj, uint32_t n_actors,
+                            uint32_t actor_bytes, uint32_t key_bytes, uint32_t inner_key_bytes, uint32_t val_bytes,
+                            uint8_t* d_out, const uint64_t* d_out_off, size_t out_bytes, void* stream) {
+  if (!ctx || !slab || n_actors == 0 || n_actors > 128 ||
+      !bc_widths_ok(actor_bytes, key_bytes, inner_key_bytes, val_bytes) || !map_map_codec_caps_ok(slab, true))
+    return CRDT_EINVAL;
+  if (n_obj && (!map_map_ptrs_ok(slab) || !d_out || !d_out_off)) return CRDT_EINVAL;
+  if (n_obj && out_bytes < 24u) return CRDT_EINVAL;  // the smallest blob (the empty map) is 24 bytes
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_map_map_bincode_egest(*slab, n_obj, n_actors, actor_bytes, key_bytes, inner_key_bytes, val_bytes,
+                                      nullptr, d_out, d_out_off, out_bytes, ctx->d_status, S(stream));
+}
+
 }  // extern "C"

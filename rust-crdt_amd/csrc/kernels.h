@@ -152,5 +152,20 @@ int launch_map_bincode_egest(const crdt_map_mvreg_slab& S, uint64_t n_obj, uint3
 int launch_mvreg_bincode_egest(const uint32_t* sn, const uint64_t* sclk, const uint64_t* sval, uint32_t cap,
                                uint64_t n_obj, uint32_t A, uint32_t wa, uint32_t wv, uint64_t* sizes, uint8_t* out,
                                const uint64_t* ooff, uint64_t out_bytes, int* status, hipStream_t stream);
+// The same for Map<u64, Orswot> (wm: member bytes) and the nested map (wk2:
+// inner key bytes) over their slabs.
+int launch_map_orswot_bincode_ingest(const uint8_t* blobs, uint64_t blob_bytes, const uint64_t* boff,
+                                     const uint64_t* blen, uint64_t n_obj, uint32_t wa, uint32_t wk, uint32_t wm,
+                                     uint32_t A, const crdt_map_orswot_slab& R, int* status, hipStream_t stream);
+int launch_map_orswot_bincode_egest(const crdt_map_orswot_slab& S, uint64_t n_obj, uint32_t A, uint32_t wa,
+                                    uint32_t wk, uint32_t wm, uint64_t* sizes, uint8_t* out, const uint64_t* ooff,
+                                    uint64_t out_bytes, int* status, hipStream_t stream);
+int launch_map_map_bincode_ingest(const uint8_t* blobs, uint64_t blob_bytes, const uint64_t* boff,
+                                  const uint64_t* blen, uint64_t n_obj, uint32_t wa, uint32_t wk, uint32_t wk2,
+                                  uint32_t wv, uint32_t A, const crdt_map_map_slab& R, int* status,
+                                  hipStream_t stream);
+int launch_map_map_bincode_egest(const crdt_map_map_slab& S, uint64_t n_obj, uint32_t A, uint32_t wa, uint32_t wk,
+                                 uint32_t wk2, uint32_t wv, uint64_t* sizes, uint8_t* out, const uint64_t* ooff,
+                                 uint64_t out_bytes, int* status, hipStream_t stream);
 
 }  // namespace crdts_hip

@@ -2,6 +2,9 @@
 // and of a Map<K, MVReg<V, A>, A> and the dense slabs of crdt_mvreg_merge /
 // crdt_map_mvreg_merge (include/crdts_hip.h). SURVEY.md §8(f) rank 1, after
 // bincode.hip (the Orswot codec).
+// Further down: the same for the two Map types whose values are containers,
+// Map<K, Orswot<M, A>, A> and Map<K, Map<K2, MVReg<V, A>, A>, A>, over
+// crdt_map_orswot_slab / crdt_map_map_slab with the helpers of this file.
 //
 // The reference form is `to_binary(&x)` = bincode 0.9 of the serde derives
 // (src/lib.rs:62-83; MVReg src/mvreg.rs:42-46, Map src/map.rs:81-99, Entry
@@ -40,18 +43,25 @@ constexpr uint32_t kWaves = 4;       // waves per block
 constexpr uint32_t kStage = 4096;    // LDS window per wave: blobs of <= kStage - 32 bytes
 constexpr uint32_t kRowMax = 128;    // dense rows up to this many actors are built in LDS
 constexpr uint32_t kDefMax = 64;     // deferred clocks per map (crdt_map_mvreg_merge's per-side limit)
+constexpr uint32_t kNestMax = 256;   // members / deferred clocks per nested set or map (crdt_map_orswot_merge's)
 
 // One wave's LDS: the blob window, the dense row under construction (all zero
 // between two clocks) and the deferred clocks' positions, sizes and ranks.
-struct alignas(16) WaveLds {
+// N: the deferred clocks (Map<u64, Orswot>: or the members of a nested set,
+// Pd / Ld its member clock, Ps the member, Rd its rank) one table holds.
+template <uint32_t N>
+struct alignas(16) WaveLdsT {
+  static constexpr uint32_t kDef = N;
   v4u stage[kStage / 16];
   uint64_t row[kRowMax];
-  uint64_t Pd[kDefMax];  // first pair of deferred clock d
-  uint64_t Ps[kDefMax];  // first key of its set
-  uint32_t Ld[kDefMax];  // its pairs
-  uint32_t Ls[kDefMax];  // its keys
-  uint32_t Rd[kDefMax];  // its rank in CLOCK ORDER
+  uint64_t Pd[N];  // first pair of deferred clock d
+  uint64_t Ps[N];  // first key of its set
+  uint32_t Ld[N];  // its pairs
+  uint32_t Ls[N];  // its keys
+  uint32_t Rd[N];  // its rank in CLOCK ORDER
 };
+typedef WaveLdsT<kDefMax> WaveLds;
+typedef WaveLdsT<kNestMax> NestLds;
 
 struct Widths {
   uint32_t wa, wk, wv;  // actor, key, value bytes
@@ -230,15 +240,15 @@ __device__ __forceinline__ int walk_mvreg(const SRC& B, uint64_t& p, uint64_t le
   return 0;
 }
 
-// One Map<K, MVReg> blob into row i of R (the nested map's inner rows are
-// such rows too). Only the used slots are written. 0 or CRDT_E* (the row is
-// then unspecified).
-template <class SRC>
-__device__ __forceinline__ int ingest_map(const SRC& B, uint64_t len, Widths W, uint32_t A,
-                                          const crdt_map_mvreg_slab& R, uint64_t i, WaveLds* X, uint32_t lane) {
+// One Map<K, MVReg> at p into row i of R; p moves past it. whole: the map is
+// the blob (bytes after it are trailing bytes); else it is an inner map of
+// the nested map and the blob goes on. Only the used slots are written. 0 or
+// CRDT_E* (the row is then unspecified).
+template <class SRC, class LDS>
+__device__ __forceinline__ int ingest_map(const SRC& B, uint64_t& p, uint64_t len, bool whole, Widths W, uint32_t A,
+                                          const crdt_map_mvreg_slab& R, uint64_t i, LDS* X, uint32_t lane) {
   const uint32_t wa = W.wa, wk = W.wk, wv = W.wv;
   const uint64_t sa = wa + 8u;
-  uint64_t p = 0;
   bool bad = false;
   uint32_t nc;
   if (!take_clock(B, p, len, wa, A, nc)) return CRDT_ENONCANON;
@@ -287,7 +297,7 @@ __device__ __forceinline__ int ingest_map(const SRC& B, uint64_t len, Widths W, 
     }
     p += ns * wk;
   }
-  if (p != len) return CRDT_ENONCANON;  // trailing bytes
+  if (whole && p != len) return CRDT_ENONCANON;  // trailing bytes
   if (nd) {
     wsync();
     // rank by comparison count: lane d counts the clocks below clock d
@@ -376,11 +386,13 @@ __global__ __launch_bounds__(kW* kWaves) void map_bincode_ingest_kernel(
       const uint32_t d = stage_blob(X->stage, blobs, blob_bytes, off, len, lane);
       wsync();
       const Src<true> B{(const uint8_t*)X->stage, d};
-      rc = MAP ? ingest_map(B, len, W, A, R, i, X, lane)
+      uint64_t p = 0;
+      rc = MAP ? ingest_map(B, p, len, true, W, A, R, i, X, lane)
                : ingest_mvreg(B, len, W.wa, W.wv, A, outn, outclk, outval, cap, i, X, lane);
     } else {
       const Src<false> B{blobs + off};
-      rc = MAP ? ingest_map(B, len, W, A, R, i, X, lane)
+      uint64_t p = 0;
+      rc = MAP ? ingest_map(B, p, len, true, W, A, R, i, X, lane)
                : ingest_mvreg(B, len, W.wa, W.wv, A, outn, outclk, outval, cap, i, X, lane);
     }
     rc = (int)uni32((uint32_t)rc);
@@ -626,6 +638,502 @@ __global__ __launch_bounds__(kW* kWaves) void map_bincode_egest_kernel(
   }
 }
 
+// ---------------------------------------- Map<u64, Orswot> and the nested map
+// The two Map types whose values are containers (crdt_map_orswot_slab,
+// crdt_map_map_slab). Format, after the Map form above:
+//
+//   Orswot   VClock clock
+//            u64 n_mem | n_mem x (M member | VClock)        HashMap: any order
+//            u64 n_def | n_def x (VClock | u64 n | n x M)   HashMap of HashSet:
+//                                             clocks and members in any order
+//   Map<K, Orswot>          entries: K key | VClock | Orswot
+//   Map<K, Map<K2, MVReg>>  entries: K key | VClock | Map<K2, MVReg> (the Map form)
+//
+// Ingest sorts what the reference leaves unordered, all by comparison count
+// out of one table of kNestMax positions: lane l ranks elements l, l + 64, ...
+// A tie is a duplicate.
+struct NWidths {
+  uint32_t wa, wk, wx, wv;  // actor, key, member / inner key, value bytes
+};
+
+// A deferred section at p (u64 n | n x (VClock | u64 n | n x E), E of we
+// bytes): the clocks ranked into CLOCK ORDER into dclock[dcap][A], their sets
+// into dset_n[dcap] / dset[dcap][scap] — HASHSET: sorted ascending by rank (a
+// HashSet, <= kNestMax elements), else copied and checked strictly ascending
+// (a BTreeSet). p moves past the section; n = the clocks. 0 or CRDT_E*.
+template <bool HASHSET, class SRC, class LDS>
+__device__ __forceinline__ int walk_deferred(const SRC& B, uint64_t& p, uint64_t len, uint32_t wa, uint32_t we,
+                                             uint32_t A, uint64_t* dclock, uint32_t* dset_n, uint64_t* dset,
+                                             uint32_t dcap, uint32_t scap, uint32_t& n, bool& bad, LDS* X,
+                                             uint32_t lane) {
+  const uint64_t sa = wa + 8u;
+  uint64_t nd;
+  if (!take_len(B, p, len, 16u, nd)) return CRDT_ENONCANON;
+  if (nd > dcap || nd > LDS::kDef) return CRDT_ECAPACITY;
+  wsync();  // the table's earlier readers are done
+  for (uint32_t d = 0; d < (uint32_t)nd; ++d) {
+    uint32_t nc;
+    if (!take_clock(B, p, len, wa, A, nc)) return CRDT_ENONCANON;
+    const uint64_t pc = p;
+    p += nc * sa;
+    uint64_t ns;
+    if (!take_len(B, p, len, we, ns)) return CRDT_ENONCANON;
+    if (ns > scap) return CRDT_ECAPACITY;
+    if (lane == 0u) {
+      X->Pd[d] = pc;
+      X->Ld[d] = nc;
+      X->Ps[d] = p;
+      X->Ls[d] = (uint32_t)ns;
+    }
+    p += ns * we;
+  }
+  n = (uint32_t)nd;
+  if (!nd) return 0;
+  wsync();
+  bool dup = false;
+  for (uint32_t d = lane; d < (uint32_t)nd; d += kW) {
+    const uint64_t pm = X->Pd[d];
+    const uint32_t lm = X->Ld[d];
+    uint32_t r = 0;
+    for (uint32_t f = 0; f < (uint32_t)nd; ++f) {
+      if (f == d) continue;
+      const int c = clock_cmp(B, X->Pd[f], X->Ld[f], pm, lm, wa);
+      r += c < 0 ? 1u : 0u;
+      dup = dup || c == 0;  // structurally equal HashMap keys
+    }
+    X->Rd[d] = r;
+  }
+  if (__ballot(dup)) return CRDT_ENONCANON;
+  wsync();
+  for (uint32_t d = 0; d < (uint32_t)nd; ++d) {
+    const uint64_t slot = uni32(X->Rd[d]);  // ranks are distinct and < nd
+    const uint64_t pc = uni64(X->Pd[d]), ps = uni64(X->Ps[d]);
+    const uint32_t lc = uni32(X->Ld[d]), ls = uni32(X->Ls[d]);
+    bad = put_clock(B, pc, lc, wa, A, dclock + slot * A, X->row, lane) || bad;
+    for (uint32_t j = lane; j < ls; j += kW) {
+      const uint64_t k = B.get(ps + (uint64_t)j * we, we);
+      if (HASHSET) {
+        uint32_t r = 0;
+        for (uint32_t f = 0; f < ls; ++f) {
+          const uint64_t x = B.get(ps + (uint64_t)f * we, we);
+          r += x < k ? 1u : 0u;
+          bad = bad || (x == k && f != j);  // two equal members: their ranks tie (and stay < ls)
+        }
+        dset[slot * scap + r] = k;
+      } else {
+        bad = bad || (j && B.get(ps + (uint64_t)(j - 1u) * we, we) >= k);
+        dset[slot * scap + j] = k;
+      }
+    }
+    if (lane == 0u) dset_n[slot] = ls;
+  }
+  return 0;
+}
+
+// One Map<K, Orswot> blob into row i of R: only the used slots. 0 or CRDT_E*.
+template <class SRC>
+__device__ __forceinline__ int ingest_obj(const SRC& B, uint64_t len, NWidths W, uint32_t A,
+                                          const crdt_map_orswot_slab& R, uint64_t i, NestLds* X, uint32_t lane) {
+  const uint32_t wa = W.wa, wk = W.wk, wm = W.wx;
+  const uint64_t sa = wa + 8u;
+  uint64_t p = 0;
+  bool bad = false;
+  uint32_t nc;
+  if (!take_clock(B, p, len, wa, A, nc)) return CRDT_ENONCANON;
+  bad = put_clock(B, p, nc, wa, A, R.clock + i * A, X->row, lane);
+  p += nc * sa;
+  // entries: BTreeMap order; an entry is at least its key, two clocks and two length words
+  uint64_t ne;
+  if (!take_len(B, p, len, wk + 32u, ne)) return CRDT_ENONCANON;
+  if (ne > R.kcap) return CRDT_ECAPACITY;
+  uint64_t prev = 0;
+  for (uint32_t e = 0; e < (uint32_t)ne; ++e) {
+    const uint64_t slot = i * R.kcap + e;
+    if (len - p < wk) return CRDT_ENONCANON;
+    const uint64_t key = uni64(B.get(p, wk));
+    p += wk;
+    if (e && key <= prev) return CRDT_ENONCANON;
+    prev = key;
+    if (!take_clock(B, p, len, wa, A, nc)) return CRDT_ENONCANON;
+    bad = put_clock(B, p, nc, wa, A, R.eclock + slot * A, X->row, lane) || bad;
+    p += nc * sa;
+    if (!take_clock(B, p, len, wa, A, nc)) return CRDT_ENONCANON;
+    bad = put_clock(B, p, nc, wa, A, R.vclock + slot * A, X->row, lane) || bad;
+    p += nc * sa;
+    // members: a HashMap, any order; sorted by rank, each clock row with its member
+    uint64_t nm;
+    if (!take_len(B, p, len, wm + 8u, nm)) return CRDT_ENONCANON;
+    if (nm > R.mcap || nm > kNestMax) return CRDT_ECAPACITY;
+    wsync();  // the table's earlier readers are done
+    for (uint32_t j = 0; j < (uint32_t)nm; ++j) {
+      if (len - p < wm) return CRDT_ENONCANON;
+      const uint64_t x = B.get(p, wm);
+      p += wm;
+      if (!take_clock(B, p, len, wa, A, nc)) return CRDT_ENONCANON;
+      if (lane == 0u) {
+        X->Ps[j] = x;
+        X->Pd[j] = p;
+        X->Ld[j] = nc;
+      }
+      p += nc * sa;
+    }
+    if (nm) {
+      wsync();
+      bool dup = false;
+      for (uint32_t j = lane; j < (uint32_t)nm; j += kW) {
+        const uint64_t x = X->Ps[j];
+        uint32_t r = 0;
+        for (uint32_t f = 0; f < (uint32_t)nm; ++f) {
+          const uint64_t y = X->Ps[f];
+          r += y < x ? 1u : 0u;
+          dup = dup || (y == x && f != j);
+        }
+        X->Rd[j] = r;
+      }
+      if (__ballot(dup)) return CRDT_ENONCANON;  // two equal members
+      wsync();
+      for (uint32_t j = 0; j < (uint32_t)nm; ++j) {
+        const uint64_t ms = slot * R.mcap + uni32(X->Rd[j]);  // ranks are distinct and < nm
+        bad = put_clock(B, uni64(X->Pd[j]), uni32(X->Ld[j]), wa, A, R.vmclock + ms * A, X->row, lane) || bad;
+        if (lane == 0u) R.vmem[ms] = X->Ps[j];
+      }
+    }
+    uint32_t nv = 0;
+    const int rc = walk_deferred<true>(B, p, len, wa, wm, A, R.vdclock + slot * R.vdcap * A, R.vdset_n + slot * R.vdcap,
+                                       R.vdset + slot * R.vdcap * R.vscap, R.vdcap, R.vscap, nv, bad, X, lane);
+    if (rc) return rc;
+    if (lane == 0u) {
+      R.keys[slot] = key;
+      R.vn_mem[slot] = (uint32_t)nm;
+      R.vn_def[slot] = nv;
+    }
+  }
+  uint32_t nd = 0;
+  const int rc = walk_deferred<false>(B, p, len, wa, wk, A, R.dclock + i * R.dcap * A, R.dset_n + i * R.dcap,
+                                      R.dset + i * R.dcap * R.scap, R.dcap, R.scap, nd, bad, X, lane);
+  if (rc) return rc;
+  if (p != len) return CRDT_ENONCANON;  // trailing bytes
+  if (lane == 0u) {
+    R.n_keys[i] = (uint32_t)ne;
+    R.n_def[i] = nd;
+  }
+  return __ballot(bad) ? CRDT_ENONCANON : 0;
+}
+
+// One Map<K, Map<K2, MVReg>> blob into row i of R, inner map k as row
+// i * kcap + k of R.inner: only the used slots. 0 or CRDT_E*.
+template <class SRC>
+__device__ __forceinline__ int ingest_obj(const SRC& B, uint64_t len, NWidths W, uint32_t A,
+                                          const crdt_map_map_slab& R, uint64_t i, NestLds* X, uint32_t lane) {
+  const uint32_t wa = W.wa, wk = W.wk;
+  const uint64_t sa = wa + 8u;
+  uint64_t p = 0;
+  bool bad = false;
+  uint32_t nc;
+  if (!take_clock(B, p, len, wa, A, nc)) return CRDT_ENONCANON;
+  bad = put_clock(B, p, nc, wa, A, R.clock + i * A, X->row, lane);
+  p += nc * sa;
+  // entries: an entry is at least its key, its clock and the empty inner map (24 bytes)
+  uint64_t ne;
+  if (!take_len(B, p, len, wk + 32u, ne)) return CRDT_ENONCANON;
+  if (ne > R.kcap) return CRDT_ECAPACITY;
+  uint64_t prev = 0;
+  for (uint32_t e = 0; e < (uint32_t)ne; ++e) {
+    const uint64_t slot = i * R.kcap + e;
+    if (len - p < wk) return CRDT_ENONCANON;
+    const uint64_t key = uni64(B.get(p, wk));
+    p += wk;
+    if (e && key <= prev) return CRDT_ENONCANON;
+    prev = key;
+    if (!take_clock(B, p, len, wa, A, nc)) return CRDT_ENONCANON;
+    bad = put_clock(B, p, nc, wa, A, R.eclock + slot * A, X->row, lane) || bad;
+    p += nc * sa;
+    wsync();  // the table's earlier readers are done
+    const int rc = ingest_map(B, p, len, false, Widths{wa, W.wx, W.wv}, A, R.inner, slot, X, lane);
+    if (rc) return rc;
+    if (lane == 0u) R.keys[slot] = key;
+  }
+  uint32_t nd = 0;
+  const int rc = walk_deferred<false>(B, p, len, wa, wk, A, R.dclock + i * R.dcap * A, R.dset_n + i * R.dcap,
+                                      R.dset + i * R.dcap * R.scap, R.dcap, R.scap, nd, bad, X, lane);
+  if (rc) return rc;
+  if (p != len) return CRDT_ENONCANON;  // trailing bytes
+  if (lane == 0u) {
+    R.n_keys[i] = (uint32_t)ne;
+    R.n_def[i] = nd;
+  }
+  return __ballot(bad) ? CRDT_ENONCANON : 0;
+}
+
+// SLAB: crdt_map_orswot_slab or crdt_map_map_slab; blobs -> rows of R.
+template <class SLAB>
+__global__ __launch_bounds__(kW* kWaves) void nested_bincode_ingest_kernel(
+    const uint8_t* __restrict__ blobs, uint64_t blob_bytes, const uint64_t* __restrict__ boff,
+    const uint64_t* __restrict__ blen, uint64_t n_obj, NWidths W, uint32_t A, SLAB R, int* __restrict__ status) {
+  __shared__ NestLds lds[kWaves];
+  const uint32_t lane = threadIdx.x & (kW - 1u), wave = threadIdx.x / kW;
+  NestLds* X = &lds[wave];
+  for (uint32_t a = lane; a < kRowMax; a += kW) X->row[a] = 0ull;
+  wsync();
+  const uint64_t n_waves = (uint64_t)gridDim.x * kWaves;
+  for (uint64_t i = (uint64_t)blockIdx.x * kWaves + wave; i < n_obj; i += n_waves) {
+    const uint64_t off = uni64(boff[i]), len = uni64(blen[i]);
+    int rc;
+    if (off > blob_bytes || len > blob_bytes - off) {
+      rc = CRDT_ENONCANON;  // the blob is not inside the buffer: nothing of it is read
+    } else if (len + 32u <= kStage) {
+      wsync();  // the previous object's window readers are done
+      const uint32_t d = stage_blob(X->stage, blobs, blob_bytes, off, len, lane);
+      wsync();
+      rc = ingest_obj(Src<true>{(const uint8_t*)X->stage, d}, len, W, A, R, i, X, lane);
+    } else {
+      rc = ingest_obj(Src<false>{blobs + off}, len, W, A, R, i, X, lane);
+    }
+    rc = (int)uni32((uint32_t)rc);
+    if (rc && lane == 0u) atomicCAS(status, 0, rc);
+  }
+}
+
+// ------------------------------------------------ egest, one level down
+// One lane: the bytes of deferred entry `slot` (clock, length word, set of we-
+// byte elements); bad: a set above scap, an element or actor that does not fit.
+__device__ __forceinline__ uint64_t lane_def_size(const uint64_t* dclock, const uint32_t* dset_n, const uint64_t* dset,
+                                                  uint64_t slot, uint32_t scap, uint32_t A, uint32_t wa, uint32_t we,
+                                                  uint32_t amax, bool& bad) {
+  uint32_t ns = dset_n[slot];
+  if (ns > scap) {
+    bad = true;
+    ns = 0u;
+  }
+  if (we < 8u)
+    for (uint32_t j = 0; j < ns; ++j) bad = bad || !fits(dset[slot * scap + j], we);
+  return 8u + (uint64_t)(wa + 8u) * lane_row_nnz(dclock + slot * A, A, amax, bad) + 8u + (uint64_t)ns * we;
+}
+
+// One lane's share of the pairs of n dense rows laid end to end (coalesced).
+__device__ __forceinline__ uint32_t flat_nnz(const uint64_t* rows, uint32_t n, uint32_t A, uint32_t amax, bool& bad,
+                                             uint32_t lane) {
+  uint32_t c = 0;
+  for (uint32_t x = lane; x < n * A; x += kW) {  // n <= 512 rows of A <= 128
+    const bool nz = rows[x] != 0ull;
+    c += nz ? 1u : 0u;
+    bad = bad || (nz && x % A >= amax);
+  }
+  return c;
+}
+
+// n deferred entries from slot d0 on, at o + p, in slab order; returns the position after them.
+__device__ __forceinline__ uint64_t write_deferred(uint8_t* o, uint64_t p, const uint64_t* dclock,
+                                                   const uint32_t* dset_n, const uint64_t* dset, uint64_t d0,
+                                                   uint32_t n, uint32_t scap, uint32_t A, uint32_t wa, uint32_t we,
+                                                   uint32_t lane) {
+  if (lane == 0u) wr(o, p, n, 8);
+  p += 8u;
+  for (uint32_t d = 0; d < n; ++d) {
+    const uint64_t slot = d0 + d;
+    p = write_clock(o, p, dclock + slot * A, A, wa, lane);
+    const uint32_t ns = uni32(dset_n[slot]);
+    if (lane == 0u) wr(o, p, ns, 8);
+    p += 8u;
+    for (uint32_t j = lane; j < ns; j += kW) wr(o, p + (uint64_t)j * we, dset[slot * scap + j], we);
+    p += (uint64_t)ns * we;
+  }
+  return p;
+}
+
+// The blob bytes of row i of a Map<u64, Orswot> slab (wave-uniform): the wave
+// goes key by key and counts each nested set's pairs over its member rows laid
+// end to end. bad: a count above its capacity or a key, member or actor that
+// does not fit its width.
+__device__ __forceinline__ uint64_t obj_size(const crdt_map_orswot_slab& S, uint64_t i, NWidths W, uint32_t A,
+                                             uint32_t amax, bool& bad_out, uint32_t lane) {
+  const uint32_t wk = W.wk, wm = W.wx;
+  const uint32_t nk = uni32(S.n_keys[i]), nd = uni32(S.n_def[i]);
+  if (nk > S.kcap || nd > S.dcap) {
+    bad_out = true;
+    return 0u;
+  }
+  const uint64_t sa = W.wa + 8u;
+  bool bad = false;
+  uint64_t fixed = 24u, pairs = 0, mine = 0;  // wave-uniform bytes; this lane's pairs and bytes
+  for (uint32_t k = 0; k < nk; ++k) {
+    const uint64_t slot = i * S.kcap + k;
+    const uint32_t nm = uni32(S.vn_mem[slot]), nv = uni32(S.vn_def[slot]);
+    if (nm > S.mcap || nv > S.vdcap) {
+      bad = true;
+      continue;
+    }
+    fixed += wk + 32u + (uint64_t)nm * (wm + 8u);
+    pairs += flat_nnz(S.vmclock + slot * S.mcap * A, nm, A, amax, bad, lane);
+    if (wm < 8u)
+      for (uint32_t j = lane; j < nm; j += kW) bad = bad || !fits(S.vmem[slot * S.mcap + j], wm);
+    for (uint32_t d = lane; d < nv; d += kW)
+      mine += lane_def_size(S.vdclock, S.vdset_n, S.vdset, slot * S.vdcap + d, S.vscap, A, W.wa, wm, amax, bad);
+  }
+  for (uint32_t d = lane; d < nd; d += kW)
+    mine += lane_def_size(S.dclock, S.dset_n, S.dset, i * S.dcap + d, S.scap, A, W.wa, wk, amax, bad);
+  // the map clock, and the keys' entry clocks and top clocks, each laid end to end
+  pairs += flat_nnz(S.clock + i * A, 1u, A, amax, bad, lane);
+  pairs += flat_nnz(S.eclock + i * S.kcap * A, nk, A, amax, bad, lane);
+  pairs += flat_nnz(S.vclock + i * S.kcap * A, nk, A, amax, bad, lane);
+  if (wk < 8u)
+    for (uint32_t k = lane; k < nk; k += kW) bad = bad || !fits(S.keys[i * S.kcap + k], wk);
+  const uint64_t total = fixed + wave_sum(mine + sa * pairs);
+  bad_out = __ballot(bad) != 0ull;
+  return uni64(total);
+}
+
+// Row i as a blob at o (its size and fit are checked), every container in slab order.
+__device__ __forceinline__ void obj_write(const crdt_map_orswot_slab& S, uint64_t i, NWidths W, uint32_t A,
+                                          uint32_t amax, uint8_t* o, uint32_t lane) {
+  const uint32_t wa = W.wa, wk = W.wk, wm = W.wx;
+  const uint32_t nk = uni32(S.n_keys[i]), nd = uni32(S.n_def[i]);
+  uint64_t p = write_clock(o, 0u, S.clock + i * A, A, wa, lane);
+  if (lane == 0u) wr(o, p, nk, 8);
+  p += 8u;
+  for (uint32_t k = 0; k < nk; ++k) {
+    const uint64_t slot = i * S.kcap + k;
+    if (lane == 0u) wr(o, p, S.keys[slot], wk);
+    p = write_clock(o, p + wk, S.eclock + slot * A, A, wa, lane);
+    p = write_clock(o, p, S.vclock + slot * A, A, wa, lane);
+    const uint32_t nm = uni32(S.vn_mem[slot]);
+    if (lane == 0u) wr(o, p, nm, 8);
+    p += 8u;
+    for (uint32_t j = 0; j < nm; ++j) {
+      if (lane == 0u) wr(o, p, S.vmem[slot * S.mcap + j], wm);
+      p = write_clock(o, p + wm, S.vmclock + (slot * S.mcap + j) * A, A, wa, lane);
+    }
+    p = write_deferred(o, p, S.vdclock, S.vdset_n, S.vdset, slot * S.vdcap, uni32(S.vn_def[slot]), S.vscap, A, wa, wm,
+                       lane);
+  }
+  write_deferred(o, p, S.dclock, S.dset_n, S.dset, i * S.dcap, nd, S.scap, A, wa, wk, lane);
+}
+
+// The bytes of row r of a Map<u64, MVReg> slab as an inner map of the nested
+// map, counted like a nested set: the wave-uniform bytes into fixed, this
+// lane's pairs and bytes into pairs / mine. (map_size gives a lane a whole
+// entry; here the wave reads the entry clocks and each register's rows laid
+// end to end.)
+__device__ __forceinline__ void inner_size(const crdt_map_mvreg_slab& S, uint64_t r, Widths W, uint32_t A,
+                                           uint32_t amax, uint64_t& fixed, uint64_t& pairs, uint64_t& mine, bool& bad,
+                                           uint32_t lane) {
+  const uint32_t wk = W.wk, wv = W.wv;
+  const uint32_t nk = uni32(S.n_keys[r]), nd = uni32(S.n_def[r]);
+  if (nk > S.kcap || nd > S.dcap) {
+    bad = true;
+    return;
+  }
+  fixed += 24u + (uint64_t)nk * (wk + 16u);
+  pairs += flat_nnz(S.clock + r * A, 1u, A, amax, bad, lane);
+  pairs += flat_nnz(S.eclock + r * S.kcap * A, nk, A, amax, bad, lane);
+  if (wk < 8u)
+    for (uint32_t k = lane; k < nk; k += kW) bad = bad || !fits(S.keys[r * S.kcap + k], wk);
+  for (uint32_t k = 0; k < nk; ++k) {
+    const uint64_t slot = r * S.kcap + k;
+    const uint32_t nv = uni32(S.mv_n[slot]);
+    if (nv > S.mcap) {
+      bad = true;
+      continue;
+    }
+    fixed += (uint64_t)nv * (8u + wv);
+    pairs += flat_nnz(S.mv_clock + slot * S.mcap * A, nv, A, amax, bad, lane);
+    if (wv < 8u)
+      for (uint32_t v = lane; v < nv; v += kW) bad = bad || !fits(S.mv_val[slot * S.mcap + v], wv);
+  }
+  for (uint32_t d = lane; d < nd; d += kW)
+    mine += lane_def_size(S.dclock, S.dset_n, S.dset, r * S.dcap + d, S.scap, A, W.wa, wk, amax, bad);
+}
+
+// Row r of a Map<u64, MVReg> slab at o + p, field after field; returns the position after it.
+__device__ __forceinline__ uint64_t inner_write(const crdt_map_mvreg_slab& S, uint64_t r, Widths W, uint32_t A,
+                                                uint8_t* o, uint64_t p, uint32_t lane) {
+  const uint32_t wa = W.wa, wk = W.wk, wv = W.wv;
+  const uint32_t nk = uni32(S.n_keys[r]), nd = uni32(S.n_def[r]);
+  p = write_clock(o, p, S.clock + r * A, A, wa, lane);
+  if (lane == 0u) wr(o, p, nk, 8);
+  p += 8u;
+  for (uint32_t k = 0; k < nk; ++k) {
+    const uint64_t slot = r * S.kcap + k;
+    if (lane == 0u) wr(o, p, S.keys[slot], wk);
+    p = write_clock(o, p + wk, S.eclock + slot * A, A, wa, lane);
+    const uint32_t nv = uni32(S.mv_n[slot]);
+    if (lane == 0u) wr(o, p, nv, 8);
+    p += 8u;
+    for (uint32_t v = 0; v < nv; ++v) {
+      p = write_clock(o, p, S.mv_clock + (slot * S.mcap + v) * A, A, wa, lane);
+      if (lane == 0u) wr(o, p, S.mv_val[slot * S.mcap + v], wv);
+      p += wv;
+    }
+  }
+  return write_deferred(o, p, S.dclock, S.dset_n, S.dset, r * S.dcap, nd, S.scap, A, wa, wk, lane);
+}
+
+// The same for the nested map: a key's bytes are its inner map's.
+__device__ __forceinline__ uint64_t obj_size(const crdt_map_map_slab& S, uint64_t i, NWidths W, uint32_t A,
+                                             uint32_t amax, bool& bad_out, uint32_t lane) {
+  const uint32_t wk = W.wk;
+  const uint32_t nk = uni32(S.n_keys[i]), nd = uni32(S.n_def[i]);
+  if (nk > S.kcap || nd > S.dcap) {
+    bad_out = true;
+    return 0u;
+  }
+  const uint64_t sa = W.wa + 8u;
+  const Widths WI{W.wa, W.wx, W.wv};
+  bool bad = false;
+  uint64_t fixed = 24u + (uint64_t)nk * (wk + 8u), pairs = 0, mine = 0;
+  pairs += flat_nnz(S.clock + i * A, 1u, A, amax, bad, lane);
+  pairs += flat_nnz(S.eclock + i * S.kcap * A, nk, A, amax, bad, lane);
+  if (wk < 8u)
+    for (uint32_t k = lane; k < nk; k += kW) bad = bad || !fits(S.keys[i * S.kcap + k], wk);
+  for (uint32_t k = 0; k < nk; ++k) inner_size(S.inner, i * S.kcap + k, WI, A, amax, fixed, pairs, mine, bad, lane);
+  for (uint32_t d = lane; d < nd; d += kW)
+    mine += lane_def_size(S.dclock, S.dset_n, S.dset, i * S.dcap + d, S.scap, A, W.wa, wk, amax, bad);
+  const uint64_t total = fixed + wave_sum(mine + sa * pairs);
+  bad_out = __ballot(bad) != 0ull;
+  return uni64(total);
+}
+
+__device__ __forceinline__ void obj_write(const crdt_map_map_slab& S, uint64_t i, NWidths W, uint32_t A,
+                                          uint32_t amax, uint8_t* o, uint32_t lane) {
+  const uint32_t wa = W.wa, wk = W.wk;
+  const uint32_t nk = uni32(S.n_keys[i]), nd = uni32(S.n_def[i]);
+  const Widths WI{wa, W.wx, W.wv};
+  uint64_t p = write_clock(o, 0u, S.clock + i * A, A, wa, lane);
+  if (lane == 0u) wr(o, p, nk, 8);
+  p += 8u;
+  for (uint32_t k = 0; k < nk; ++k) {
+    const uint64_t slot = i * S.kcap + k;
+    if (lane == 0u) wr(o, p, S.keys[slot], wk);
+    p = write_clock(o, p + wk, S.eclock + slot * A, A, wa, lane);
+    p = inner_write(S.inner, slot, WI, A, o, p, lane);
+  }
+  write_deferred(o, p, S.dclock, S.dset_n, S.dset, i * S.dcap, nd, S.scap, A, wa, wk, lane);
+}
+
+// WRITE: blob i at out + ooff[i]; else sizes[i] = its bytes (0: an object in error).
+template <class SLAB, bool WRITE>
+__global__ __launch_bounds__(kW* kWaves) void nested_bincode_egest_kernel(
+    SLAB S, uint64_t n_obj, NWidths W, uint32_t A, uint64_t* __restrict__ sizes, uint8_t* __restrict__ out,
+    const uint64_t* __restrict__ ooff, uint64_t out_bytes, int* __restrict__ status) {
+  const uint32_t lane = threadIdx.x & (kW - 1u), wave = threadIdx.x / kW;
+  const uint32_t amax = W.wa >= 4u ? 0xFFFFFFFFu : 1u << (8u * W.wa);
+  const uint64_t n_waves = (uint64_t)gridDim.x * kWaves;
+  for (uint64_t i = (uint64_t)blockIdx.x * kWaves + wave; i < n_obj; i += n_waves) {
+    bool bad = false;
+    const uint64_t size = obj_size(S, i, W, A, amax, bad, lane);
+    int rc = bad ? CRDT_ENONCANON : 0;
+    if (WRITE && !rc) {
+      const uint64_t oo = uni64(ooff[i]);
+      if (oo > out_bytes || size > out_bytes - oo) rc = CRDT_ECAPACITY;  // the placed blob leaves the buffer
+      else obj_write(S, i, W, A, amax, out + oo, lane);
+    }
+    if (lane == 0u) {
+      if (!WRITE) sizes[i] = rc ? 0ull : size;
+      if (rc) atomicCAS(status, 0, rc);
+    }
+  }
+}
+
 uint32_t grid_for(uint64_t n_obj, uint32_t blocks_per_cu) {
   int dev = 0, cus = 256;
   if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
@@ -684,6 +1192,56 @@ int launch_mvreg_bincode_egest(const uint32_t* sn, const uint64_t* sclk, const u
     hipLaunchKernelGGL((map_bincode_egest_kernel<false, false>), grid, block, 0, stream, kNoSlab, sn, sclk, sval, cap,
                        n_obj, W, A, sizes, nullptr, nullptr, 0u, status);
   return hipGetLastError() == hipSuccess ? CRDT_OK : CRDT_EHIP;
+}
+
+namespace {
+template <class SLAB>
+int nested_ingest(const uint8_t* blobs, uint64_t blob_bytes, const uint64_t* boff, const uint64_t* blen,
+                  uint64_t n_obj, NWidths W, uint32_t A, const SLAB& R, int* status, hipStream_t stream) {
+  if (n_obj == 0) return CRDT_OK;
+  // 48 KB of LDS per block: three blocks per CU
+  hipLaunchKernelGGL((nested_bincode_ingest_kernel<SLAB>), dim3(grid_for(n_obj, 3u)), dim3(kW * kWaves), 0, stream,
+                     blobs, blob_bytes, boff, blen, n_obj, W, A, R, status);
+  return hipGetLastError() == hipSuccess ? CRDT_OK : CRDT_EHIP;
+}
+template <class SLAB>
+int nested_egest(const SLAB& S, uint64_t n_obj, NWidths W, uint32_t A, uint64_t* sizes, uint8_t* out,
+                 const uint64_t* ooff, uint64_t out_bytes, int* status, hipStream_t stream) {
+  if (n_obj == 0) return CRDT_OK;
+  const dim3 grid(grid_for(n_obj, 8u)), block(kW * kWaves);
+  if (out)
+    hipLaunchKernelGGL((nested_bincode_egest_kernel<SLAB, true>), grid, block, 0, stream, S, n_obj, W, A, nullptr, out,
+                       ooff, out_bytes, status);
+  else
+    hipLaunchKernelGGL((nested_bincode_egest_kernel<SLAB, false>), grid, block, 0, stream, S, n_obj, W, A, sizes,
+                       nullptr, nullptr, 0u, status);
+  return hipGetLastError() == hipSuccess ? CRDT_OK : CRDT_EHIP;
+}
+}  // namespace
+
+int launch_map_orswot_bincode_ingest(const uint8_t* blobs, uint64_t blob_bytes, const uint64_t* boff,
+                                     const uint64_t* blen, uint64_t n_obj, uint32_t wa, uint32_t wk, uint32_t wm,
+                                     uint32_t A, const crdt_map_orswot_slab& R, int* status, hipStream_t stream) {
+  return nested_ingest(blobs, blob_bytes, boff, blen, n_obj, NWidths{wa, wk, wm, 1u}, A, R, status, stream);
+}
+
+int launch_map_orswot_bincode_egest(const crdt_map_orswot_slab& S, uint64_t n_obj, uint32_t A, uint32_t wa,
+                                    uint32_t wk, uint32_t wm, uint64_t* sizes, uint8_t* out, const uint64_t* ooff,
+                                    uint64_t out_bytes, int* status, hipStream_t stream) {
+  return nested_egest(S, n_obj, NWidths{wa, wk, wm, 1u}, A, sizes, out, ooff, out_bytes, status, stream);
+}
+
+int launch_map_map_bincode_ingest(const uint8_t* blobs, uint64_t blob_bytes, const uint64_t* boff,
+                                  const uint64_t* blen, uint64_t n_obj, uint32_t wa, uint32_t wk, uint32_t wk2,
+                                  uint32_t wv, uint32_t A, const crdt_map_map_slab& R, int* status,
+                                  hipStream_t stream) {
+  return nested_ingest(blobs, blob_bytes, boff, blen, n_obj, NWidths{wa, wk, wk2, wv}, A, R, status, stream);
+}
+
+int launch_map_map_bincode_egest(const crdt_map_map_slab& S, uint64_t n_obj, uint32_t A, uint32_t wa, uint32_t wk,
+                                 uint32_t wk2, uint32_t wv, uint64_t* sizes, uint8_t* out, const uint64_t* ooff,
+                                 uint64_t out_bytes, int* status, hipStream_t stream) {
+  return nested_egest(S, n_obj, NWidths{wa, wk, wk2, wv}, A, sizes, out, ooff, out_bytes, status, stream);
 }
 
 }  // namespace crdts_hip

@@ -11,5 +11,7 @@ for wl in orswot apply mvreg map; do
 done
 timeout -k 10 500 python tools/map_bincode_bench.py --out profiles/map_bincode_bench.json > $OUT/map_bincode_bench.log 2>&1 || { echo BENCH_FAILED map_bincode; exit 1; }
 echo "map_bincode $(cut -c1-160 profiles/map_bincode_bench.json)"
+timeout -k 10 500 python tools/nested_bincode_bench.py --out profiles/nested_bincode_bench.json > $OUT/nested_bincode_bench.log 2>&1 || { echo BENCH_FAILED nested_bincode; exit 1; }
+echo "nested_bincode $(cut -c1-160 profiles/nested_bincode_bench.json)"
 for wl in apply mvreg map; do bash tools/profile_workload.sh r01e $wl || { echo PROF_FAILED $wl; exit 1; }; done
 echo ALL_OK
