@@ -155,6 +155,132 @@ int crdt_pncounter_csr_merge(crdt_ctx* ctx, const crdt_clock_csr* self_p, const 
                              const crdt_clock_csr_out* out_p, const crdt_clock_csr_out* out_n, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * Batched op path of the clocks and counters (clock_ops.hip): CmRDT::apply,
+ * Causal::truncate, the reads, and the two primitives the reference builds
+ * the rest from (subtract, intersection), on dense rows and on CSR runs.
+ *
+ * A batch of dots (or, for the get calls, of queried actors) grouped per
+ * object; within an object the order never matters (witness is a max).
+ *
+ * Every call: CRDT_EINVAL (before any device work) for a null ctx, a null
+ * struct, a null array with n_obj > 0 (a null op array whose count says it is
+ * non-empty), n_actors == 0 (dense calls), an output aliasing an input.
+ * Otherwise n_obj == 0 is CRDT_OK. Per-object faults latch on the context
+ * (crdt_ctx_status) and leave the other objects untouched; nothing outside
+ * the described arrays is read or written.
+ * ------------------------------------------------------------------------ */
+typedef struct crdt_clock_ops {   /* all device arrays */
+  const uint64_t* obj_end;  /* n_obj: object i's ops are [obj_end[i-1], obj_end[i]) */
+  const uint32_t* actor;    /* n_ops */
+  const uint64_t* counter;  /* n_ops (unused by the get calls) */
+  const uint32_t* dir;      /* n_ops, PNCounter only: 0 = Dir::Pos, 1 = Dir::Neg; else may be null */
+  size_t n_ops;
+} crdt_clock_ops;
+
+/* Dense rows (the layout of crdt_vclock_dense_merge), in place on d_self.
+ *
+ * crdt_vclock_dense_apply / crdt_gcounter_apply: VClock::apply == witness
+ * (src/vclock.rs:126-128, 159-163), GCounter::apply (src/gcounter.rs:53-55):
+ * row[i][actor] = max(row[i][actor], counter) for each of object i's dots. A
+ * repeated actor keeps its largest counter; a dot with counter 0 is a no-op;
+ * rows of objects without ops are neither read nor written.
+ * crdt_pncounter_apply: PNCounter::apply (src/pncounter.rs:82-87) on [P|N]
+ * rows: dir 0 -> slot actor, dir 1 -> slot n_actors + actor.
+ * Latched CRDT_ENONCANON: an actor >= n_actors, a dir above 1 (the op is
+ * skipped, the object's other ops still apply), an object whose range
+ * [obj_end[i-1], obj_end[i]) decreases or runs past n_ops (the object is
+ * skipped; the others apply their ranges).
+ * CRDT_EINVAL also for a null counter array (a null dir array, PNCounter)
+ * with n_ops > 0, and for d_self equal to an op array. */
+int crdt_vclock_dense_apply(crdt_ctx* ctx, uint64_t* d_self, const crdt_clock_ops* ops, size_t n_obj,
+                            uint32_t n_actors, void* stream);
+int crdt_gcounter_apply(crdt_ctx* ctx, uint64_t* d_self, const crdt_clock_ops* ops, size_t n_obj,
+                        uint32_t n_actors, void* stream);
+int crdt_pncounter_apply(crdt_ctx* ctx, uint64_t* d_self, const crdt_clock_ops* ops, size_t n_obj,
+                         uint32_t n_actors, void* stream);
+
+/* crdt_vclock_dense_truncate: Causal::truncate (src/vclock.rs:103-120):
+ *   self[k] = min(self[k], other[k]) (absent is 0: an actor missing on either
+ *   side disappears).
+ * crdt_vclock_dense_subtract: VClock::subtract (src/vclock.rs:236-242):
+ *   self[k] = other[k] >= self[k] ? 0 : self[k].
+ * crdt_vclock_dense_intersection: VClock::intersection (src/vclock.rs:219-228):
+ *   self[k] = self[k] == other[k] ? self[k] : 0.
+ * Flat over n_obj * n_actors words like the merge (24 B of traffic per slot).
+ * CRDT_EINVAL also for d_self == d_other. */
+int crdt_vclock_dense_truncate(crdt_ctx* ctx, uint64_t* d_self, const uint64_t* d_other, size_t n_obj,
+                               uint32_t n_actors, void* stream);
+int crdt_vclock_dense_subtract(crdt_ctx* ctx, uint64_t* d_self, const uint64_t* d_other, size_t n_obj,
+                               uint32_t n_actors, void* stream);
+int crdt_vclock_dense_intersection(crdt_ctx* ctx, uint64_t* d_self, const uint64_t* d_other, size_t n_obj,
+                                   uint32_t n_actors, void* stream);
+
+/* crdt_gcounter_value: GCounter::value (src/gcounter.rs:76-78): d_out[i] =
+ * the wrapping u64 sum of row i.
+ * crdt_pncounter_value: PNCounter::value (src/pncounter.rs:117-119) of [P|N]
+ * rows: d_out[i] = (int64_t)sumP - (int64_t)sumN, wrapping.
+ * CRDT_EINVAL also for d_out == d_rows. */
+int crdt_gcounter_value(crdt_ctx* ctx, const uint64_t* d_rows, uint64_t* d_out, size_t n_obj, uint32_t n_actors,
+                        void* stream);
+int crdt_pncounter_value(crdt_ctx* ctx, const uint64_t* d_rows, int64_t* d_out, size_t n_obj, uint32_t n_actors,
+                         void* stream);
+
+/* crdt_vclock_dense_get: VClock::get (src/vclock.rs:206-210): d_out[j] =
+ * row[i][queries.actor[j]] for object i's queries j (d_out has
+ * queries.n_ops words; counter and dir are not read). An actor >= n_actors
+ * reads 0 without latching (an absent actor is 0). VClock::inc (:182-185) is
+ * get + 1, left to the caller. A query outside every object's range (an
+ * obj_end decreasing or past n_ops latches CRDT_ENONCANON) is not written.
+ * CRDT_EINVAL also for d_out equal to d_rows or to a query array. */
+int crdt_vclock_dense_get(crdt_ctx* ctx, const uint64_t* d_rows, const crdt_clock_ops* queries, uint64_t* d_out,
+                          size_t n_obj, uint32_t n_actors, void* stream);
+
+/* CSR clocks (crdt_clock_csr / crdt_clock_csr_out above), never in place.
+ * Placement and canonical-form checks and their latched codes are those of
+ * crdt_vclock_csr_merge: a misplaced run latches CRDT_EINVAL, a non-canonical
+ * run CRDT_ENONCANON, and out.len[i] is 0 in both cases.
+ *
+ * crdt_vclock_csr_truncate / _subtract / _intersection: a filter of self's
+ * run by other's —
+ *   truncate (src/vclock.rs:103-120) keeps actors present on both sides, with
+ *     the smaller counter;
+ *   subtract (:236-242) drops actors where other's counter is >= self's;
+ *   intersection (:219-228) keeps actors whose counter is equal on both sides.
+ * out.off[i] := self.off[i], out.len[i] <= self.len[i]; out.n_entries >=
+ * self.n_entries suffices (CRDT_ECAPACITY otherwise) and the output is a
+ * valid (gapped) input batch. CRDT_EINVAL also for self.n_obj != other.n_obj
+ * and for an out array equal to an array of self or other.
+ *
+ * crdt_vclock_csr_apply / crdt_gcounter_csr_apply: out[i] = self's run after
+ * witnessing object i's dots (VClock::apply src/vclock.rs:126-128, GCounter::
+ * apply src/gcounter.rs:53-55). The op list is unsorted and may repeat
+ * actors; a counter-0 dot creates no entry. out.off[i] := self.off[i] +
+ * obj_end[i-1], out.len[i] <= self.len[i] + (ops of i); out.n_entries >=
+ * self.n_entries + ops.n_ops suffices (CRDT_ECAPACITY otherwise). An object
+ * without ops is copied through. An obj_end that decreases or runs past
+ * n_ops latches CRDT_ENONCANON (out.len 0). ops.dir is not read. */
+int crdt_vclock_csr_truncate(crdt_ctx* ctx, const crdt_clock_csr* self, const crdt_clock_csr* other,
+                             const crdt_clock_csr_out* out, void* stream);
+int crdt_vclock_csr_subtract(crdt_ctx* ctx, const crdt_clock_csr* self, const crdt_clock_csr* other,
+                             const crdt_clock_csr_out* out, void* stream);
+int crdt_vclock_csr_intersection(crdt_ctx* ctx, const crdt_clock_csr* self, const crdt_clock_csr* other,
+                                 const crdt_clock_csr_out* out, void* stream);
+int crdt_vclock_csr_apply(crdt_ctx* ctx, const crdt_clock_csr* self, const crdt_clock_ops* ops,
+                          const crdt_clock_csr_out* out, void* stream);
+int crdt_gcounter_csr_apply(crdt_ctx* ctx, const crdt_clock_csr* self, const crdt_clock_ops* ops,
+                            const crdt_clock_csr_out* out, void* stream);
+
+/* crdt_gcounter_csr_value: GCounter::value (src/gcounter.rs:76-78): d_out[i]
+ * = the wrapping u64 sum of run i (0 for a run out of [0, n_entries), which
+ * latches CRDT_EINVAL). Canonical form is not checked: a sum needs none.
+ * crdt_vclock_csr_get: VClock::get (src/vclock.rs:206-210): d_out[j] = the
+ * counter of queries.actor[j] in object i's run, by binary search (the run is
+ * taken as sorted); an absent actor reads 0. */
+int crdt_gcounter_csr_value(crdt_ctx* ctx, const crdt_clock_csr* self, uint64_t* d_out, void* stream);
+int crdt_vclock_csr_get(crdt_ctx* ctx, const crdt_clock_csr* self, const crdt_clock_ops* queries, uint64_t* d_out,
+                        void* stream);
+
+/* ------------------------------------------------------------------------ *
  * Orswot canonical record (one object = one contiguous, self-describing
  * record; a batch = a byte buffer + a u64 byte offset per object).
  *

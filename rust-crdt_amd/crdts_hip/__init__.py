@@ -25,7 +25,7 @@ __all__ = [
     "Engine", "OrswotBatch", "GenParams", "CrdtError", "generate_orswot", "generate_dense", "HostOrswot",
     "Orswot", "VClock", "GCounter", "PNCounter", "merge_batch", "decode_record", "encode_record",
     "record_bytes", "CONFIG3", "EXPORTS", "LIB_PATH", "CONFIG5", "SPARSE_CLOCK", "generate_replicas", "ClockBatch",
-    "generate_clocks_csr", "MapMapSlab", "MapOps", "MapMapOps", "MVRegOps",
+    "generate_clocks_csr", "MapMapSlab", "MapOps", "MapMapOps", "MVRegOps", "ClockOps",
 ]
 
 # SURVEY.md §8(d) config 3 / BASELINE.json configs[2].
@@ -335,6 +335,70 @@ class MVRegOps:
     def from_lists(cls, per_obj, device=0):
         """per_obj[i] = [(clock_pairs, val), ...]"""
         return cls.from_arrays(*cls.arrays_from_lists(per_obj), device=device)
+
+
+class ClockOps:
+    """A batch of dots for the clocks' op path (crdt_clock_ops), grouped per
+    object: VClock::apply / GCounter::apply take (actor, counter) dots
+    (src/vclock.rs:126-128, src/gcounter.rs:53-55), PNCounter::apply
+    (src/pncounter.rs:82-87) also a direction (0 = Dir::Pos, 1 = Dir::Neg); the
+    get calls read the actors only. Tensors: obj_end int64 [n_obj], actor int32
+    [n_ops], counter int64 [n_ops] (u64 bits), dir int32 [n_ops] or None.
+    `host` keeps the numpy arrays the batch was packed from (None when it was
+    built from device tensors)."""
+
+    def __init__(self, obj_end, actor, counter, dir_=None, host=None):
+        self.t = (obj_end, actor, counter, dir_)
+        self.n_obj = int(obj_end.numel())
+        self.n_ops = int(actor.numel())
+        self.host = host
+
+    def cops(self):
+        from ._lib import ClockOpsC
+
+        p = [C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None for t in self.t]
+        return ClockOpsC(*p, self.n_ops)
+
+    @classmethod
+    def from_arrays(cls, obj_end, actor, counter=None, dir_=None, device=0):
+        """Host numpy arrays (u64 / u32 as in crdt_clock_ops) -> device; not
+        validated. counter None: zeros (a query batch); device None: the
+        tensors stay on the host."""
+        torch = _torch()
+        obj_end = np.ascontiguousarray(np.asarray(obj_end, dtype=np.uint64))
+        actor = np.ascontiguousarray(np.asarray(actor, dtype=np.uint32))
+        counter = np.zeros(actor.size, np.uint64) if counter is None else \
+            np.ascontiguousarray(np.asarray(counter, dtype=np.uint64))
+        dir_ = None if dir_ is None else np.ascontiguousarray(np.asarray(dir_, dtype=np.uint32))
+
+        def put(x):
+            if x is None:
+                return None
+            t = torch.from_numpy(x.view(np.int32 if x.dtype == np.uint32 else np.int64))
+            return t if device is None else t.to(f"cuda:{device}")
+
+        return cls(put(obj_end), put(actor), put(counter), put(dir_), host=(obj_end, actor, counter, dir_))
+
+    @staticmethod
+    def arrays_from_lists(per_obj, with_dir=False):
+        """per_obj[i] = [(actor, counter), ...] — or [(actor, counter, dir), ...]
+        with with_dir, or bare actors for a query batch — -> (obj_end u64
+        [n_obj], actor u32 [n_ops], counter u64 [n_ops], dir u32 [n_ops] or None)."""
+        ends, act, ctr, dr = [], [], [], []
+        for ops in per_obj:
+            for op in ops:
+                op = op if isinstance(op, (tuple, list)) else (op, 0)
+                act.append(op[0]); ctr.append(op[1])
+                if with_dir:
+                    dr.append(op[2])
+            ends.append(len(act))
+        return (np.asarray(ends, np.uint64), np.asarray(act, np.uint32), np.asarray(ctr, np.uint64),
+                np.asarray(dr, np.uint32) if with_dir else None)
+
+    @classmethod
+    def from_lists(cls, per_obj, with_dir=False, device=0):
+        """per_obj[i] = object i's dots, see arrays_from_lists."""
+        return cls.from_arrays(*cls.arrays_from_lists(per_obj, with_dir), device=device)
 
 
 class MapMapOps:
@@ -1631,6 +1695,178 @@ class Engine:
         return self_rows
 
 
+    # ------------------------------------------------ the clocks' op path
+    def dense_apply(self, rows, ops: "ClockOps", n_actors, kind="vclock", stream=None, check_status=True):
+        """In place: row i witnesses object i's dots (VClock::apply
+        src/vclock.rs:126-128; GCounter::apply src/gcounter.rs:53-55;
+        PNCounter::apply src/pncounter.rs:82-87 on [P|N] rows, ops with dir)."""
+        fn = {"vclock": lib.crdt_vclock_dense_apply, "gcounter": lib.crdt_gcounter_apply,
+              "pncounter": lib.crdt_pncounter_apply}[kind]
+        slots = n_actors * (2 if kind == "pncounter" else 1)
+        if rows.numel() != ops.n_obj * slots:
+            raise CrdtError(-1, "dense rows shape mismatch")
+        c = ops.cops()
+        check(fn(self.ctx, C.c_void_p(rows.data_ptr()), C.byref(c), ops.n_obj, n_actors, self._stream(stream)),
+              f"dense apply ({kind})")
+        if check_status:
+            self.status(stream)
+        return rows
+
+    def _dense_binop(self, fn, what, self_rows, other_rows, n_actors, stream):
+        if self_rows.numel() != other_rows.numel() or self_rows.numel() % n_actors:
+            raise CrdtError(-1, "dense rows shape mismatch")
+        check(fn(self.ctx, C.c_void_p(self_rows.data_ptr()), C.c_void_p(other_rows.data_ptr()),
+                 self_rows.numel() // n_actors, n_actors, self._stream(stream)), what)
+        return self_rows
+
+    def dense_truncate(self, self_rows, other_rows, n_actors, stream=None):
+        """In place: Causal::truncate (src/vclock.rs:103-120), the pointwise min."""
+        return self._dense_binop(lib.crdt_vclock_dense_truncate, "dense truncate", self_rows, other_rows, n_actors,
+                                 stream)
+
+    def dense_subtract(self, self_rows, other_rows, n_actors, stream=None):
+        """In place: VClock::subtract (src/vclock.rs:236-242)."""
+        return self._dense_binop(lib.crdt_vclock_dense_subtract, "dense subtract", self_rows, other_rows, n_actors,
+                                 stream)
+
+    def dense_intersection(self, self_rows, other_rows, n_actors, stream=None):
+        """In place: VClock::intersection (src/vclock.rs:219-228)."""
+        return self._dense_binop(lib.crdt_vclock_dense_intersection, "dense intersection", self_rows, other_rows,
+                                 n_actors, stream)
+
+    def _dense_value(self, fn, what, rows, slots, n_actors, out, stream):
+        torch = _torch()
+        if rows.numel() % slots:
+            raise CrdtError(-1, "dense rows shape mismatch")
+        n_obj = rows.numel() // slots
+        out = out if out is not None else torch.empty(n_obj, dtype=torch.int64, device=rows.device)
+        check(fn(self.ctx, C.c_void_p(rows.data_ptr()), C.c_void_p(out.data_ptr()), n_obj, n_actors,
+                 self._stream(stream)), what)
+        return out
+
+    def gcounter_value(self, rows, n_actors, out=None, stream=None):
+        """GCounter::value (src/gcounter.rs:76-78): int64 tensor holding the wrapping u64 row sums."""
+        return self._dense_value(lib.crdt_gcounter_value, "gcounter value", rows, n_actors, n_actors, out, stream)
+
+    def pncounter_value(self, rows, n_actors, out=None, stream=None):
+        """PNCounter::value (src/pncounter.rs:117-119) of [P|N] rows: int64 per object."""
+        return self._dense_value(lib.crdt_pncounter_value, "pncounter value", rows, 2 * n_actors, n_actors, out,
+                                 stream)
+
+    def dense_get(self, rows, queries: "ClockOps", n_actors, out=None, stream=None, check_status=True):
+        """VClock::get (src/vclock.rs:206-210) per queried actor: int64 tensor
+        [queries.n_ops] of u64 counters, 0 for an absent actor. VClock::inc
+        (:182-185) is this + 1."""
+        torch = _torch()
+        if rows.numel() != queries.n_obj * n_actors:
+            raise CrdtError(-1, "dense rows shape mismatch")
+        out = out if out is not None else torch.empty(max(1, queries.n_ops), dtype=torch.int64, device=rows.device)
+        c = queries.cops()
+        check(lib.crdt_vclock_dense_get(self.ctx, C.c_void_p(rows.data_ptr()), C.byref(c),
+                                        C.c_void_p(out.data_ptr()), queries.n_obj, n_actors, self._stream(stream)),
+              "dense get")
+        if check_status:
+            self.status(stream)
+        return out[: queries.n_ops]
+
+    def _csr_out(self, n_obj, cap):
+        torch = _torch()
+        dev = f"cuda:{self.device}"
+        cap = max(1, cap)
+        return ClockBatch(torch.empty(n_obj, dtype=torch.int64, device=dev),
+                          torch.empty(n_obj, dtype=torch.int32, device=dev),
+                          torch.empty(cap, dtype=torch.int32, device=dev),
+                          torch.empty(cap, dtype=torch.int64, device=dev), n_entries=cap)
+
+    def _csr_filter(self, fn, what, S, O, out, stream, check_status):
+        from ._lib import ClockCsrOut
+
+        out = out or self._csr_out(S.n_obj, S.n_entries)
+        s, o = S.cstruct(), O.cstruct()
+        w = ClockCsrOut(out.off.data_ptr(), out.len.data_ptr(), out.act.data_ptr(), out.ctr.data_ptr(), out.n_entries)
+        check(fn(self.ctx, C.byref(s), C.byref(o), C.byref(w), self._stream(stream)), what)
+        if check_status:
+            self.status(stream)
+        return out
+
+    def clock_csr_truncate(self, S: "ClockBatch", O: "ClockBatch", out=None, stream=None, check_status=True):
+        """out[i] = S[i] after Causal::truncate(&O[i]) (src/vclock.rs:103-120), placed at S.off."""
+        return self._csr_filter(lib.crdt_vclock_csr_truncate, "csr truncate", S, O, out, stream, check_status)
+
+    def clock_csr_subtract(self, S: "ClockBatch", O: "ClockBatch", out=None, stream=None, check_status=True):
+        """out[i] = S[i] after subtract(&O[i]) (src/vclock.rs:236-242), placed at S.off."""
+        return self._csr_filter(lib.crdt_vclock_csr_subtract, "csr subtract", S, O, out, stream, check_status)
+
+    def clock_csr_intersection(self, S: "ClockBatch", O: "ClockBatch", out=None, stream=None, check_status=True):
+        """out[i] = S[i].intersection(&O[i]) (src/vclock.rs:219-228), placed at S.off."""
+        return self._csr_filter(lib.crdt_vclock_csr_intersection, "csr intersection", S, O, out, stream,
+                                check_status)
+
+    def clock_csr_apply(self, S: "ClockBatch", ops: "ClockOps", out=None, kind="vclock", stream=None,
+                        check_status=True):
+        """out[i] = S[i] after witnessing object i's dots (VClock::apply
+        src/vclock.rs:126-128; GCounter::apply src/gcounter.rs:53-55), placed
+        at S.off[i] + (ops before i)."""
+        from ._lib import ClockCsrOut
+
+        if ops.n_obj != S.n_obj:
+            raise CrdtError(-1, "clock_csr_apply: one op list per object")
+        out = out or self._csr_out(S.n_obj, S.n_entries + ops.n_ops)
+        s, c = S.cstruct(), ops.cops()
+        w = ClockCsrOut(out.off.data_ptr(), out.len.data_ptr(), out.act.data_ptr(), out.ctr.data_ptr(), out.n_entries)
+        fn = {"vclock": lib.crdt_vclock_csr_apply, "gcounter": lib.crdt_gcounter_csr_apply}[kind]
+        check(fn(self.ctx, C.byref(s), C.byref(c), C.byref(w), self._stream(stream)), f"{kind}_csr_apply")
+        if check_status:
+            self.status(stream)
+        return out
+
+    def clock_csr_value(self, S: "ClockBatch", out=None, stream=None, check_status=True):
+        """GCounter::value (src/gcounter.rs:76-78) of sparse counters: int64 tensor of wrapping u64 sums."""
+        torch = _torch()
+        out = out if out is not None else torch.empty(max(1, S.n_obj), dtype=torch.int64, device=S.off.device)
+        s = S.cstruct()
+        check(lib.crdt_gcounter_csr_value(self.ctx, C.byref(s), C.c_void_p(out.data_ptr()), self._stream(stream)),
+              "csr value")
+        if check_status:
+            self.status(stream)
+        return out[: S.n_obj]
+
+    def clock_csr_get(self, S: "ClockBatch", queries: "ClockOps", out=None, stream=None, check_status=True):
+        """VClock::get (src/vclock.rs:206-210) per queried actor over sparse clocks."""
+        torch = _torch()
+        if queries.n_obj != S.n_obj:
+            raise CrdtError(-1, "clock_csr_get: one query list per object")
+        out = out if out is not None else torch.empty(max(1, queries.n_ops), dtype=torch.int64, device=S.off.device)
+        s, c = S.cstruct(), queries.cops()
+        check(lib.crdt_vclock_csr_get(self.ctx, C.byref(s), C.byref(c), C.c_void_p(out.data_ptr()),
+                                      self._stream(stream)), "csr get")
+        if check_status:
+            self.status(stream)
+        return out[: queries.n_ops]
+
+    def pncounter_csr_apply(self, SP: "ClockBatch", SN: "ClockBatch", ops: "ClockOps", stream=None,
+                            check_status=True):
+        """PNCounter::apply (src/pncounter.rs:82-87) over sparse P and N clocks:
+        the ops are split by dir on the host and applied as two batches;
+        returns (out_p, out_n)."""
+        if ops.host is None or ops.host[3] is None:
+            raise CrdtError(-1, "pncounter_csr_apply: ops packed from host arrays with dir")
+        ends, act, ctr, dr = ops.host
+        obj = np.repeat(np.arange(ends.size), np.diff(ends.astype(np.int64), prepend=0))
+        outs = []
+        for d, S in ((0, SP), (1, SN)):
+            m = dr == d
+            sub_ends = np.cumsum(np.bincount(obj[m], minlength=ends.size)).astype(np.uint64)
+            sub = ClockOps.from_arrays(sub_ends, act[m], ctr[m], device=self.device)
+            outs.append(self.clock_csr_apply(S, sub, kind="gcounter", stream=stream, check_status=check_status))
+        return tuple(outs)
+
+    def pncounter_csr_value(self, SP: "ClockBatch", SN: "ClockBatch", stream=None, check_status=True):
+        """PNCounter::value (src/pncounter.rs:117-119) over sparse P and N clocks: int64 per object."""
+        return (self.clock_csr_value(SP, stream=stream, check_status=check_status) -
+                self.clock_csr_value(SN, stream=stream, check_status=check_status))
+
+
 # -------------------------------------------------------------- generators
 def _params(p):
     if isinstance(p, GenParams):
@@ -1991,6 +2227,24 @@ class VClock:
 
     def merge(self, other, engine=None):
         merge_batch([self], [other], engine)
+
+    def truncate(self, other):  # Causal::truncate, src/vclock.rs:103-120
+        kept = {}
+        for a, c in self.dots.items():
+            m = min(c, other.get(a))
+            if m > 0:
+                kept[a] = m
+        self.dots = kept
+
+    def subtract(self, other):  # src/vclock.rs:236-242
+        for a, c in other.dots.items():
+            if c >= self.get(a):
+                self.dots.pop(a, None)
+
+    def intersection(self, other):  # src/vclock.rs:219-228
+        v = VClock(n_actors=self.n_actors)
+        v.dots = {a: c for a, c in self.dots.items() if other.get(a) == c}
+        return v
 
     def row(self, n):
         r = np.zeros(n, dtype=np.uint64)

@@ -86,6 +86,10 @@ EXPORTS = [
     "crdt_map_mvreg_from_bincode", "crdt_map_mvreg_bincode_sizes", "crdt_map_mvreg_to_bincode",
     "crdt_map_orswot_from_bincode", "crdt_map_orswot_bincode_sizes", "crdt_map_orswot_to_bincode",
     "crdt_map_map_from_bincode", "crdt_map_map_bincode_sizes", "crdt_map_map_to_bincode",
+    "crdt_vclock_dense_apply", "crdt_gcounter_apply", "crdt_pncounter_apply", "crdt_vclock_dense_truncate",
+    "crdt_vclock_dense_subtract", "crdt_vclock_dense_intersection", "crdt_gcounter_value", "crdt_pncounter_value",
+    "crdt_vclock_dense_get", "crdt_vclock_csr_truncate", "crdt_vclock_csr_subtract", "crdt_vclock_csr_intersection",
+    "crdt_vclock_csr_apply", "crdt_gcounter_csr_apply", "crdt_gcounter_csr_value", "crdt_vclock_csr_get",
 ]
 
 CRDT_COMM_ID_BYTES = 128
@@ -170,6 +174,11 @@ class ClockCsr(C.Structure):
     """crdt_clock_csr (include/crdts_hip.h)."""
     _fields_ = [("off", C.c_void_p), ("len", C.c_void_p), ("act", C.c_void_p), ("ctr", C.c_void_p),
                 ("n_obj", C.c_size_t), ("n_entries", C.c_size_t)]
+
+
+class ClockOpsC(C.Structure):
+    """crdt_clock_ops (include/crdts_hip.h)."""
+    _fields_ = [(f, C.c_void_p) for f in ("obj_end", "actor", "counter", "dir")] + [("n_ops", C.c_size_t)]
 
 
 class ClockCsrOut(C.Structure):
@@ -301,6 +310,22 @@ def _load():
         "crdt_vclock_csr_merge": (I, [P, C.POINTER(ClockCsr), C.POINTER(ClockCsr), C.POINTER(ClockCsrOut), P]),
         "crdt_gcounter_csr_merge": (I, [P, C.POINTER(ClockCsr), C.POINTER(ClockCsr), C.POINTER(ClockCsrOut), P]),
         "crdt_pncounter_csr_merge": (I, [P] + [C.POINTER(ClockCsr)] * 4 + [C.POINTER(ClockCsrOut)] * 2 + [P]),
+        "crdt_vclock_dense_apply": (I, [P, P, C.POINTER(ClockOpsC), SZ, U32, P]),
+        "crdt_gcounter_apply": (I, [P, P, C.POINTER(ClockOpsC), SZ, U32, P]),
+        "crdt_pncounter_apply": (I, [P, P, C.POINTER(ClockOpsC), SZ, U32, P]),
+        "crdt_vclock_dense_truncate": (I, [P, P, P, SZ, U32, P]),
+        "crdt_vclock_dense_subtract": (I, [P, P, P, SZ, U32, P]),
+        "crdt_vclock_dense_intersection": (I, [P, P, P, SZ, U32, P]),
+        "crdt_gcounter_value": (I, [P, P, P, SZ, U32, P]),
+        "crdt_pncounter_value": (I, [P, P, P, SZ, U32, P]),
+        "crdt_vclock_dense_get": (I, [P, P, C.POINTER(ClockOpsC), P, SZ, U32, P]),
+        "crdt_vclock_csr_truncate": (I, [P, C.POINTER(ClockCsr), C.POINTER(ClockCsr), C.POINTER(ClockCsrOut), P]),
+        "crdt_vclock_csr_subtract": (I, [P, C.POINTER(ClockCsr), C.POINTER(ClockCsr), C.POINTER(ClockCsrOut), P]),
+        "crdt_vclock_csr_intersection": (I, [P, C.POINTER(ClockCsr), C.POINTER(ClockCsr), C.POINTER(ClockCsrOut), P]),
+        "crdt_vclock_csr_apply": (I, [P, C.POINTER(ClockCsr), C.POINTER(ClockOpsC), C.POINTER(ClockCsrOut), P]),
+        "crdt_gcounter_csr_apply": (I, [P, C.POINTER(ClockCsr), C.POINTER(ClockOpsC), C.POINTER(ClockCsrOut), P]),
+        "crdt_gcounter_csr_value": (I, [P, C.POINTER(ClockCsr), P, P]),
+        "crdt_vclock_csr_get": (I, [P, C.POINTER(ClockCsr), C.POINTER(ClockOpsC), P, P]),
         "crdt_orswot_generate_replicas_subset": (I, [U64, SZ, SZ, C.POINTER(RepParams), U32, U32, U32, U32, I,
                                                      C.POINTER(P)]),
         "crdt_orswot_replica_join_transport": (I, [P, C.POINTER(TransportC), BP, U32, U32, P, P, SZ, C.POINTER(SZ),

@@ -211,6 +211,166 @@ int crdt_pncounter_csr_merge(crdt_ctx* ctx, const crdt_clock_csr* self_p, const 
   return launch_clock_csr_merge(s, o, w, 2, ctx->d_status, S(stream));
 }
 
+// ---- the clocks' op path (clock_ops.hip)
+namespace {
+// the op batch of an apply (need_counter; need_dir: PNCounter) or of a get
+bool clock_ops_ok(const crdt_clock_ops* p, size_t n_obj, bool need_counter, bool need_dir) {
+  if (!p || (n_obj && !p->obj_end)) return false;
+  if (p->n_ops && (!p->actor || (need_counter && !p->counter) || (need_dir && !p->dir))) return false;
+  return true;
+}
+bool clock_ops_alias(const crdt_clock_ops* p, const void* w) {
+  return w && (w == p->obj_end || w == p->actor || w == p->counter || w == p->dir);
+}
+int dense_apply(crdt_ctx* ctx, uint64_t* self, const crdt_clock_ops* ops, size_t n_obj, uint32_t n_actors, bool pn,
+                void* stream) {
+  if (!ctx || n_actors == 0 || !clock_ops_ok(ops, n_obj, true, pn) || (n_obj && !self)) return CRDT_EINVAL;
+  if (n_obj && clock_ops_alias(ops, self)) return CRDT_EINVAL;
+  if (n_obj == 0) return CRDT_OK;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_dense_clock_apply(self, *ops, pn, n_obj, n_actors, ctx->d_status, S(stream));
+}
+int dense_binop(crdt_ctx* ctx, int op, uint64_t* self, const uint64_t* other, size_t n_obj, uint32_t n_actors,
+                void* stream) {
+  if (!ctx || n_actors == 0 || (n_obj && (!self || !other || self == other))) return CRDT_EINVAL;
+  if (n_obj == 0) return CRDT_OK;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_dense_clock_binop(op, self, other, (uint64_t)n_obj * n_actors, S(stream));
+}
+int dense_value(crdt_ctx* ctx, const uint64_t* rows, uint64_t* out, size_t n_obj, uint32_t n_actors, bool pn,
+                void* stream) {
+  if (!ctx || n_actors == 0 || (n_obj && (!rows || !out || (const uint64_t*)out == rows))) return CRDT_EINVAL;
+  if (n_obj == 0) return CRDT_OK;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_dense_clock_value(rows, out, pn, n_obj, n_actors, S(stream));
+}
+bool csr_in_ok(const crdt_clock_csr* s) {
+  return s && !(s->n_obj && (!s->off || !s->len)) && !(s->n_entries && (!s->act || !s->ctr));
+}
+bool csr_out_ok(const crdt_clock_csr_out* w, size_t n_obj) {
+  return w && !(n_obj && (!w->off || !w->len)) && !(w->n_entries && (!w->act || !w->ctr));
+}
+bool csr_alias(const crdt_clock_csr* s, const crdt_clock_csr_out* w) {
+  const void* in[4] = {s->off, s->len, s->act, s->ctr};
+  const void* out[4] = {w->off, w->len, w->act, w->ctr};
+  for (const void* a : in)
+    for (const void* b : out)
+      if (a && a == b) return true;
+  return false;
+}
+int csr_filter(crdt_ctx* ctx, int op, const crdt_clock_csr* self, const crdt_clock_csr* other,
+               const crdt_clock_csr_out* out, void* stream) {
+  if (!ctx || !csr_in_ok(self) || !csr_in_ok(other) || self->n_obj != other->n_obj || !csr_out_ok(out, self->n_obj))
+    return CRDT_EINVAL;
+  if (self->n_obj && (csr_alias(self, out) || csr_alias(other, out))) return CRDT_EINVAL;
+  if (out->n_entries < self->n_entries) return CRDT_ECAPACITY;
+  if (self->n_obj == 0) return CRDT_OK;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_clock_csr_filter(op, *self, *other, *out, ctx->d_status, S(stream));
+}
+}  // namespace
+
+int crdt_vclock_dense_apply(crdt_ctx* ctx, uint64_t* d_self, const crdt_clock_ops* ops, size_t n_obj,
+                            uint32_t n_actors, void* stream) {
+  return dense_apply(ctx, d_self, ops, n_obj, n_actors, false, stream);
+}
+int crdt_gcounter_apply(crdt_ctx* ctx, uint64_t* d_self, const crdt_clock_ops* ops, size_t n_obj, uint32_t n_actors,
+                        void* stream) {
+  return dense_apply(ctx, d_self, ops, n_obj, n_actors, false, stream);
+}
+int crdt_pncounter_apply(crdt_ctx* ctx, uint64_t* d_self, const crdt_clock_ops* ops, size_t n_obj, uint32_t n_actors,
+                         void* stream) {
+  return dense_apply(ctx, d_self, ops, n_obj, n_actors, true, stream);
+}
+int crdt_vclock_dense_truncate(crdt_ctx* ctx, uint64_t* d_self, const uint64_t* d_other, size_t n_obj,
+                               uint32_t n_actors, void* stream) {
+  return dense_binop(ctx, kClockTruncate, d_self, d_other, n_obj, n_actors, stream);
+}
+int crdt_vclock_dense_subtract(crdt_ctx* ctx, uint64_t* d_self, const uint64_t* d_other, size_t n_obj,
+                               uint32_t n_actors, void* stream) {
+  return dense_binop(ctx, kClockSubtract, d_self, d_other, n_obj, n_actors, stream);
+}
+int crdt_vclock_dense_intersection(crdt_ctx* ctx, uint64_t* d_self, const uint64_t* d_other, size_t n_obj,
+                                   uint32_t n_actors, void* stream) {
+  return dense_binop(ctx, kClockIntersection, d_self, d_other, n_obj, n_actors, stream);
+}
+int crdt_gcounter_value(crdt_ctx* ctx, const uint64_t* d_rows, uint64_t* d_out, size_t n_obj, uint32_t n_actors,
+                        void* stream) {
+  return dense_value(ctx, d_rows, d_out, n_obj, n_actors, false, stream);
+}
+int crdt_pncounter_value(crdt_ctx* ctx, const uint64_t* d_rows, int64_t* d_out, size_t n_obj, uint32_t n_actors,
+                         void* stream) {
+  return dense_value(ctx, d_rows, (uint64_t*)d_out, n_obj, n_actors, true, stream);
+}
+int crdt_vclock_dense_get(crdt_ctx* ctx, const uint64_t* d_rows, const crdt_clock_ops* queries, uint64_t* d_out,
+                          size_t n_obj, uint32_t n_actors, void* stream) {
+  if (!ctx || n_actors == 0 || !clock_ops_ok(queries, n_obj, false, false)) return CRDT_EINVAL;
+  if (n_obj && (!d_rows || (queries->n_ops && !d_out))) return CRDT_EINVAL;
+  if (n_obj && d_out && ((const uint64_t*)d_out == d_rows || clock_ops_alias(queries, d_out))) return CRDT_EINVAL;
+  if (n_obj == 0) return CRDT_OK;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_dense_clock_get(d_rows, *queries, d_out, n_obj, n_actors, ctx->d_status, S(stream));
+}
+int crdt_vclock_csr_truncate(crdt_ctx* ctx, const crdt_clock_csr* self, const crdt_clock_csr* other,
+                             const crdt_clock_csr_out* out, void* stream) {
+  return csr_filter(ctx, kClockTruncate, self, other, out, stream);
+}
+int crdt_vclock_csr_subtract(crdt_ctx* ctx, const crdt_clock_csr* self, const crdt_clock_csr* other,
+                             const crdt_clock_csr_out* out, void* stream) {
+  return csr_filter(ctx, kClockSubtract, self, other, out, stream);
+}
+int crdt_vclock_csr_intersection(crdt_ctx* ctx, const crdt_clock_csr* self, const crdt_clock_csr* other,
+                                 const crdt_clock_csr_out* out, void* stream) {
+  return csr_filter(ctx, kClockIntersection, self, other, out, stream);
+}
+int crdt_vclock_csr_apply(crdt_ctx* ctx, const crdt_clock_csr* self, const crdt_clock_ops* ops,
+                          const crdt_clock_csr_out* out, void* stream) {
+  if (!ctx || !csr_in_ok(self) || !clock_ops_ok(ops, self->n_obj, true, false) || !csr_out_ok(out, self->n_obj))
+    return CRDT_EINVAL;
+  if (self->n_obj) {
+    if (csr_alias(self, out)) return CRDT_EINVAL;
+    for (const void* w : {(const void*)out->off, (const void*)out->len, (const void*)out->act, (const void*)out->ctr})
+      if (clock_ops_alias(ops, w)) return CRDT_EINVAL;
+  }
+  if (out->n_entries < self->n_entries + ops->n_ops) return CRDT_ECAPACITY;
+  if (self->n_obj == 0) return CRDT_OK;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  // the long paths' scratch (more than 64 dots or entries in one object)
+  if (ops->n_ops && (rc = ctx_big_scratch(ctx, clock_csr_apply_scratch_bytes(*ops)))) return rc;
+  return launch_clock_csr_apply(*self, *ops, *out, ops->n_ops ? ctx->d_big : nullptr, ctx->d_status, S(stream));
+}
+int crdt_gcounter_csr_apply(crdt_ctx* ctx, const crdt_clock_csr* self, const crdt_clock_ops* ops,
+                            const crdt_clock_csr_out* out, void* stream) {
+  return crdt_vclock_csr_apply(ctx, self, ops, out, stream);
+}
+int crdt_gcounter_csr_value(crdt_ctx* ctx, const crdt_clock_csr* self, uint64_t* d_out, void* stream) {
+  if (!ctx || !csr_in_ok(self) || (self->n_obj && (!d_out || (const uint64_t*)d_out == self->ctr ||
+                                                   (const uint64_t*)d_out == self->off)))
+    return CRDT_EINVAL;
+  if (self->n_obj == 0) return CRDT_OK;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_clock_csr_value(*self, d_out, ctx->d_status, S(stream));
+}
+int crdt_vclock_csr_get(crdt_ctx* ctx, const crdt_clock_csr* self, const crdt_clock_ops* queries, uint64_t* d_out,
+                        void* stream) {
+  if (!ctx || !csr_in_ok(self) || !clock_ops_ok(queries, self->n_obj, false, false)) return CRDT_EINVAL;
+  if (self->n_obj && queries->n_ops &&
+      (!d_out || (const uint64_t*)d_out == self->ctr || (const uint64_t*)d_out == self->off ||
+       clock_ops_alias(queries, d_out)))
+    return CRDT_EINVAL;
+  if (self->n_obj == 0) return CRDT_OK;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_clock_csr_get(*self, *queries, d_out, ctx->d_status, S(stream));
+}
+
 int crdt_orswot_truncate(crdt_ctx* ctx, const crdt_orswot_batch* self, const crdt_clock_csr* clocks,
                          uint32_t n_actors, uint32_t flags, uint8_t* d_out, uint64_t* d_out_off, size_t out_bytes,
                          void* stream) {

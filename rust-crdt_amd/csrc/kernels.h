@@ -34,6 +34,29 @@ int launch_orswot_truncate(const crdt_orswot_batch& self, const crdt_clock_csr& 
 
 int launch_dense_max(uint64_t* self, const uint64_t* other, uint64_t n_words, hipStream_t stream);
 
+// The clocks' op path (clock_ops.hip). Dense rows in place: the three binops
+// flat over n_words like launch_dense_max; apply (pn: [P|N] rows and ops.dir)
+// and get walk the op batch; value reduces rows of A (pn: 2 * A) slots.
+enum { kClockTruncate = 0, kClockSubtract = 1, kClockIntersection = 2 };
+int launch_dense_clock_binop(int op, uint64_t* self, const uint64_t* other, uint64_t n_words, hipStream_t stream);
+int launch_dense_clock_apply(uint64_t* rows, const crdt_clock_ops& ops, bool pn, uint64_t n_obj, uint32_t A,
+                             int* status, hipStream_t stream);
+int launch_dense_clock_get(const uint64_t* rows, const crdt_clock_ops& queries, uint64_t* out, uint64_t n_obj,
+                           uint32_t A, int* status, hipStream_t stream);
+int launch_dense_clock_value(const uint64_t* rows, uint64_t* out, bool pn, uint64_t n_obj, uint32_t A,
+                             hipStream_t stream);
+// CSR runs, out != in: the filters place out at self's offsets, apply at
+// self.off + obj_end[i-1]; apply's scratch holds clock_csr_apply_scratch_bytes
+// (null only with no ops), 8-byte aligned.
+int launch_clock_csr_filter(int op, const crdt_clock_csr& self, const crdt_clock_csr& other,
+                            const crdt_clock_csr_out& out, int* status, hipStream_t stream);
+size_t clock_csr_apply_scratch_bytes(const crdt_clock_ops& ops);
+int launch_clock_csr_apply(const crdt_clock_csr& self, const crdt_clock_ops& ops, const crdt_clock_csr_out& out,
+                           uint8_t* scratch, int* status, hipStream_t stream);
+int launch_clock_csr_value(const crdt_clock_csr& self, uint64_t* out, int* status, hipStream_t stream);
+int launch_clock_csr_get(const crdt_clock_csr& self, const crdt_clock_ops& queries, uint64_t* out, int* status,
+                         hipStream_t stream);
+
 int launch_orswot_validate(const uint8_t* base, const uint64_t* off, uint64_t bytes, uint64_t n_obj,
                            uint32_t n_actors, uint32_t flags, int* status, hipStream_t stream);
 
