@@ -22,6 +22,7 @@
 
 #include "../../include/crdts_hip.h"
 #include "kernels.h"
+#include "map_limits.h"
 #include "map_rows.h"
 #include "sched.h"
 
@@ -31,8 +32,10 @@ namespace {
 using namespace maprow;  // Row<NS> and the VClock ops on it (map_rows.h)
 
 constexpr uint32_t kMpW = 64;
-constexpr uint32_t kMpComb = 128;  // combined deferred entries (<= dcap_self + dcap_other, dcap <= 64)
-constexpr uint32_t kMpVals = 256;  // kept values of one key (<= mcap_self + mcap_other, mcap <= 128)
+constexpr uint32_t kMpComb = 2u * kMapMvregDcap;  // combined deferred entries (<= dcap_self + dcap_other)
+constexpr uint32_t kMpVals = 2u * kMapMvregMcap;  // kept values of one key (<= mcap_self + mcap_other)
+static_assert(kMapMvregDcap <= kMpW, "lane d holds deferred entry d's set size");
+static_assert(kMapMvregDcap <= 0xFFu && kMapMvregMcap <= 0xFFu, "comb and vals pack an index into 8 bits");
 
 __device__ __forceinline__ void mp_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -70,7 +73,7 @@ __global__ __launch_bounds__(kMpW, MINW) void map_mvreg_merge_kernel(crdt_map_mv
   __shared__ uint32_t vals[kMpVals];     // kept value slots of the key: side << 8 | slot
   __shared__ uint64_t vr[2][VS ? kVsRows : 1];  // the key's value clock rows: self, other
   __shared__ uint64_t md[kMdStage];             // the object's map deferred sets (when they fit)
-  __shared__ uint32_t mdn[2][64];               // their sizes (dcap <= 64), self / other
+  __shared__ uint32_t mdn[2][kMapMvregDcap];    // their sizes, self / other
   const uint32_t lane = threadIdx.x;
   // (sched.h; G: most tasks are empty slots, a plain stride balances them)
   typename std::conditional<G, GridStride, BlockTickets<4>>::type sched(n_obj, ctl + 3, lane);
@@ -99,7 +102,7 @@ __global__ __launch_bounds__(kMpW, MINW) void map_mvreg_merge_kernel(crdt_map_mv
     // loops below read mv_n / dset_n slots of the slab row as counts); lane k
     // keeps key k's value count (keys < 64), which the value-row stage below
     // reads by readlane (no dependent load on the per-key chain)
-    // (and its key; lane d: map deferred entry d's set size, dcap <= 64)
+    // (and its key; lane d: map deferred entry d's set size, dcap <= kMapMvregDcap)
     const uint32_t vnS = lane < nS ? S.mv_n[si * S.kcap + lane] : 0u, vnO = lane < nO ? O.mv_n[oi * O.kcap + lane] : 0u;
     const uint64_t kregS = lane < nS ? S.keys[si * S.kcap + lane] : 0ull;
     const uint64_t kregO = lane < nO ? O.keys[oi * O.kcap + lane] : 0ull;
@@ -370,9 +373,7 @@ int launch_map_mvreg_merge(const crdt_map_mvreg_slab& S, const crdt_map_mvreg_sl
                            uint64_t n_obj, uint32_t A, int* status, uint32_t* ctl, hipStream_t stream, int variant) {
   if (n_obj == 0) return CRDT_OK;
   if (hipMemsetAsync(ctl, 0, 4 * sizeof(uint32_t), stream) != hipSuccess) return CRDT_EHIP;  // ctl[3]: tickets
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const uint64_t cap = (uint64_t)cus * 28u;  // 7 single-wave blocks per SIMD
+  const uint64_t cap = (uint64_t)cu_count() * 28u;  // 7 single-wave blocks per SIMD
   const uint32_t blocks = (uint32_t)(n_obj < cap ? n_obj : cap);
   const bool vs = (uint64_t)S.mcap * A <= kVsRows && (uint64_t)O.mcap * A <= kVsRows;
   if (A > 64u)  // 65-128 actors: two slots per lane
@@ -398,18 +399,8 @@ int launch_map_mvreg_merge_tasks(const crdt_map_mvreg_slab& S, const crdt_map_mv
                                  uint64_t n_tasks, uint32_t slots, uint32_t A, int* status, uint32_t* ctl,
                                  hipStream_t stream) {
   if (n_tasks == 0) return CRDT_OK;
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const uint64_t cap = (uint64_t)cus * 28u;
-  uint32_t blocks = (uint32_t)(n_tasks < cap ? n_tasks : cap);
-  // the kept keys are an object's first slots: a grid stride coprime with the
-  // slots per object spreads them over every block (one sharing a factor
-  // with it would leave the blocks of the last slots idle)
-  auto gcd = [](uint32_t a, uint32_t b) {
-    while (b) { const uint32_t t = a % b; a = b; b = t; }
-    return a;
-  };
-  while (blocks > 1u && slots > 1u && gcd(blocks, slots) != 1u) --blocks;
+  const uint64_t cap = (uint64_t)cu_count() * 28u;
+  const uint32_t blocks = coprime_grid((uint32_t)(n_tasks < cap ? n_tasks : cap), slots);  // (sched.h)
   if (hipMemsetAsync(ctl, 0, 4 * sizeof(uint32_t), stream) != hipSuccess) return CRDT_EHIP;
   if (A > 64u)
     hipLaunchKernelGGL((map_mvreg_merge_kernel<false, 2, true>), dim3(blocks), dim3(kMpW), 0, stream, S, O, R, n_tasks,

@@ -23,14 +23,16 @@
 // consecutive iterations are ordered by each lane's own program order; the
 // per-key / per-entry counts (mv_n, dset_n) are read and written by lane 0
 // only. keys[] and dset[] are searched by all lanes: every edit ends in
-// ma_sync(). The per-op edits are map_mvreg_ws.h's (shared with the nested
-// map's op path, map_map_apply.hip, whose inner maps take them). The op headers, and the clock pairs of the first ops, are staged
-// in LDS 64 ops at a time, so that no op waits for its own header loads.
+// mw_sync() (map_wave.h). The per-op edits are map_mvreg_ws.h's (shared with
+// the nested map's op path, map_map_apply.hip, whose inner maps take them).
+// The ops are read through map_ops.h: headers, and the clock pairs of the
+// first ops, staged in LDS 64 ops at a time, each op's clock as a dense row.
 #include <hip/hip_runtime.h>
 
 #include "../../include/crdts_hip.h"
 #include "kernels.h"
 #include "map_mvreg_ws.h"
+#include "map_ops.h"
 #include "map_rows.h"
 #include "sched.h"
 
@@ -40,19 +42,13 @@ namespace {
 using namespace maprow;
 using namespace mapws;
 
-constexpr uint32_t kMaW = kW;
-__device__ __forceinline__ void ma_sync() { mw_sync(); }
-
 // (7 waves/SIMD: bounded to 72 VGPRs, the kernel keeps a few values in
 // scratch and is faster than unbounded at 5 waves/SIMD — DESIGN.md §5h)
 template <int NS>
-__global__ __launch_bounds__(kMaW, 7) void map_mvreg_apply_kernel(crdt_map_mvreg_slab S, crdt_map_mvreg_ops P,
+__global__ __launch_bounds__(kW, 7) void map_mvreg_apply_kernel(crdt_map_mvreg_slab S, crdt_map_mvreg_ops P,
                                                               crdt_map_mvreg_slab R, uint64_t n_obj, uint32_t A,
                                                               int* __restrict__ status, uint32_t* __restrict__ ctl) {
-  __shared__ uint64_t oc[128];  // the op's clock, scattered to a dense row
-  // a chunk of 64 op headers and the first 64 clock pairs of its ops
-  __shared__ uint32_t hkind[kMaW], hact[kMaW], pact[kMaW];
-  __shared__ uint64_t hkey[kMaW], hctr[kMaW], hval[kMaW], hend[kMaW], pctr[kMaW];
+  const mapops::OpStage ops = mapops::op_stage();  // the op reader's LDS stage (map_ops.h)
   const uint32_t lane = threadIdx.x;
   const uint64_t Rm = R.mcap, Rs = R.scap;
   BlockTickets<4> sched(n_obj, ctl + 3, lane);
@@ -67,13 +63,13 @@ __global__ __launch_bounds__(kMaW, 7) void map_mvreg_apply_kernel(crdt_map_mvreg
     const uint32_t vnS = lane < nS ? S.mv_n[i * S.kcap + lane] : 0u;
     const uint32_t dnS = lane < dS ? S.dset_n[i * S.dcap + lane] : 0u;
     bool bad = vnS > S.mcap || dnS > S.scap;
-    for (uint32_t k = lane + kMaW; k < nS; k += kMaW) bad = bad || S.mv_n[i * S.kcap + k] > S.mcap;
-    for (uint32_t d = lane + kMaW; d < dS; d += kMaW) bad = bad || S.dset_n[i * S.dcap + d] > S.scap;
+    for (uint32_t k = lane + kW; k < nS; k += kW) bad = bad || S.mv_n[i * S.kcap + k] > S.mcap;
+    for (uint32_t d = lane + kW; d < dS; d += kW) bad = bad || S.dset_n[i * S.dcap + d] > S.scap;
     if (__ballot(bad) != 0ull) {
       if (lane == 0u) atomicCAS(status, 0, CRDT_ENONCANON);
       continue;
     }
-    // ---- out[i]'s arrays; self[i]'s used slots copied in (out caps >= self's: api.hip)
+    // ---- out[i]'s arrays; self[i]'s used slots copied in (out caps >= self's: api.hip's out_caps_ok)
     const MapRef m = map_ref(R, i, A);
     uint64_t* const keys = m.keys;
     uint64_t* const ecl = m.ecl;
@@ -87,7 +83,7 @@ __global__ __launch_bounds__(kMaW, 7) void map_mvreg_apply_kernel(crdt_map_mvreg
     copy_n(ecl, S.eclock + i * S.kcap * A, nS * A, lane);
     for (uint32_t k = 0; k < nS; ++k) {
       const uint64_t sk = i * S.kcap + k;
-      const uint32_t vn = k < kMaW ? (uint32_t)__builtin_amdgcn_readlane(vnS, k) : uni32(S.mv_n[sk]);
+      const uint32_t vn = k < kW ? (uint32_t)__builtin_amdgcn_readlane(vnS, k) : uni32(S.mv_n[sk]);
       if (lane == 0u) mvn[k] = vn;
       copy_n(mvc + k * Rm * A, S.mv_clock + sk * S.mcap * A, vn * A, lane);
       copy_n(mvv + k * Rm, S.mv_val + sk * S.mcap, vn, lane);
@@ -95,7 +91,7 @@ __global__ __launch_bounds__(kMaW, 7) void map_mvreg_apply_kernel(crdt_map_mvreg
     copy_n(dcl, S.dclock + i * S.dcap * A, dS * A, lane);
     for (uint32_t d = 0; d < dS; ++d) {
       const uint64_t sd = i * S.dcap + d;
-      const uint32_t sn = d < kMaW ? (uint32_t)__builtin_amdgcn_readlane(dnS, d) : uni32(S.dset_n[sd]);
+      const uint32_t sn = d < kW ? (uint32_t)__builtin_amdgcn_readlane(dnS, d) : uni32(S.dset_n[sd]);
       if (lane == 0u) dsn[d] = sn;
       copy_n(dse + d * Rs, S.dset + sd * S.scap, sn, lane);
     }
@@ -104,85 +100,36 @@ __global__ __launch_bounds__(kMaW, 7) void map_mvreg_apply_kernel(crdt_map_mvreg
     st.nk = nS;
     st.nd = dS;
     int err = 0;
-    ma_sync();
+    mw_sync();
 
-    // The op headers are staged in LDS 64 ops at a time (slot t: the chunk's op
-    // t), with the first 64 clock pairs of those ops, before the chunk's edits
-    // start: these loads are independent of each other and of the state, so
-    // none sits on an op's chain of dependent round trips.
     uint64_t pb = 0ull;  // the staged pairs' first index
     for (uint64_t j = lo; j < hi && !err; ++j) {
-      const uint32_t t = (uint32_t)(j - lo) & (kMaW - 1u);
-      if (t == 0u) {
-        const bool inb = lane < hi - j;
-        const uint32_t k_ = inb ? P.kind[j + lane] : 0u, a_ = inb ? P.actor[j + lane] : 0u;
-        const uint64_t y_ = inb ? P.key[j + lane] : 0ull, c_ = inb ? P.counter[j + lane] : 0ull;
-        const uint64_t v_ = inb ? P.val[j + lane] : 0ull, e_ = inb ? P.clk_end[j + lane] : 0ull;
-        pb = j ? uni64(P.clk_end[j - 1u]) : 0ull;
-        const bool pin = pb < (uint64_t)P.n_clk && lane < (uint64_t)P.n_clk - pb;
-        const uint32_t pa_ = pin ? P.clk_act[pb + lane] : 0u;
-        const uint64_t pc_ = pin ? P.clk_ctr[pb + lane] : 0ull;
-        ma_sync();  // the previous chunk's reads of the stage are done
-        hkind[lane] = k_;
-        hact[lane] = a_;
-        hkey[lane] = y_;
-        hctr[lane] = c_;
-        hval[lane] = v_;
-        hend[lane] = e_;
-        pact[lane] = pa_;
-        pctr[lane] = pc_;
-        ma_sync();
-      }
-      const uint32_t kind = uni32(hkind[t]);
-      const uint64_t clo = t ? uni64(hend[t - 1u]) : pb, chi = uni64(hend[t]);
-      const uint64_t key = uni64(hkey[t]);
-      // an op clock is strictly increasing actors below A: at most A pairs
-      if (kind > CRDT_MAP_OP_UP || clo > chi || chi > (uint64_t)P.n_clk || chi - clo > A) {
+      const uint32_t t = (uint32_t)(j - lo) & (kW - 1u);
+      if (t == 0u) pb = mapops::refill(ops, P, P.val, j, hi, lane);
+      mapops::OpHdr h;
+      if (!mapops::read_hdr(ops, P, t, pb, CRDT_MAP_OP_UP, A, h)) {
         err = CRDT_ENONCANON;
         break;
       }
-      if (kind == CRDT_MAP_OP_NOP) continue;
-      // ---- the op's clock as a dense row (and its canonicity)
-      const uint32_t np = (uint32_t)(chi - clo);
-      ma_sync();  // the previous op's reads of oc are done
-      oc[lane] = 0ull;
-      oc[lane + kMaW] = 0ull;
-      ma_sync();
-      bool cbad = false;
-      if (chi - pb <= kMaW) {  // its pairs are staged, from slot clo - pb (clo >= pb: checked op by op)
-        const uint32_t f = (uint32_t)(clo - pb);
-        if (lane < np) {
-          const uint32_t a = pact[f + lane];
-          const uint64_t c = pctr[f + lane];
-          cbad = c == 0ull || a >= A || (lane && pact[f + lane - 1u] >= a);
-          if (a < A) oc[a] = c;
-        }
-      } else {
-        for (uint32_t p = lane; p < np; p += kMaW) {
-          const uint32_t a = P.clk_act[clo + p];
-          const uint64_t c = P.clk_ctr[clo + p];
-          cbad = cbad || c == 0ull || a >= A || (p && P.clk_act[clo + p - 1u] >= a);
-          if (a < A) oc[a] = c;
-        }
-      }
-      if (__ballot(cbad) != 0ull) {
+      if (h.kind == CRDT_MAP_OP_NOP) continue;
+      const mapops::OpClock<NS> oc = mapops::read_clock<NS>(ops, P, h, pb, A, lane);
+      if (!oc.ok) {
         err = CRDT_ENONCANON;
         break;
       }
-      ma_sync();
-      const Row<NS> C = ldrow<NS>(oc, A, lane);
+      const Row<NS>& C = oc.C;
 
-      if (kind == CRDT_MAP_OP_RM) {
-        err = map_rm<NS>(m, st, key, C, A, lane);
+      if (h.kind == CRDT_MAP_OP_RM) {
+        err = map_rm<NS>(m, st, h.key, C, A, lane);
         continue;
       }
       // ---- Op::Up
-      const uint32_t da = uni32(hact[t]);
+      const uint32_t da = uni32(ops.hact[t]);
       if (da >= A) {
         err = CRDT_ENONCANON;
         break;
       }
-      err = map_up<NS>(m, st, da, uni64(hctr[t]), key, C, uni64(hval[t]), A, lane);
+      err = map_up<NS>(m, st, da, uni64(ops.hctr[t]), h.key, C, uni64(ops.hpay[t]), A, lane);
     }
     if (err) {
       if (lane == 0u) atomicCAS(status, 0, err);
@@ -202,15 +149,13 @@ int launch_map_mvreg_apply(const crdt_map_mvreg_slab& S, const crdt_map_mvreg_op
                            uint64_t n_obj, uint32_t A, int* status, uint32_t* ctl, hipStream_t stream) {
   if (n_obj == 0) return CRDT_OK;
   if (hipMemsetAsync(ctl, 0, 4 * sizeof(uint32_t), stream) != hipSuccess) return CRDT_EHIP;  // ctl[3]: tickets
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const uint64_t cap = (uint64_t)cus * 28u;  // 7 single-wave blocks per SIMD (the kernel's register bound)
+  const uint64_t cap = (uint64_t)cu_count() * 28u;  // 7 single-wave blocks per SIMD (the kernel's register bound)
   const uint32_t blocks = (uint32_t)(n_obj < cap ? n_obj : cap);
   if (A > 64u)  // 65-128 actors: two slots per lane
-    hipLaunchKernelGGL((map_mvreg_apply_kernel<2>), dim3(blocks), dim3(kMaW), 0, stream, S, P, R, n_obj, A, status,
+    hipLaunchKernelGGL((map_mvreg_apply_kernel<2>), dim3(blocks), dim3(kW), 0, stream, S, P, R, n_obj, A, status,
                        ctl);
   else
-    hipLaunchKernelGGL((map_mvreg_apply_kernel<1>), dim3(blocks), dim3(kMaW), 0, stream, S, P, R, n_obj, A, status,
+    hipLaunchKernelGGL((map_mvreg_apply_kernel<1>), dim3(blocks), dim3(kW), 0, stream, S, P, R, n_obj, A, status,
                        ctl);
   return hipGetLastError() == hipSuccess ? CRDT_OK : CRDT_EHIP;
 }

@@ -32,6 +32,8 @@
 
 #include "../../include/crdts_hip.h"
 #include "kernels.h"
+#include "map_limits.h"
+#include "sched.h"
 
 namespace crdts_hip {
 namespace {
@@ -41,9 +43,11 @@ typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 constexpr uint32_t kW = 64;
 constexpr uint32_t kWaves = 4;       // waves per block
 constexpr uint32_t kStage = 4096;    // LDS window per wave: blobs of <= kStage - 32 bytes
-constexpr uint32_t kRowMax = 128;    // dense rows up to this many actors are built in LDS
-constexpr uint32_t kDefMax = 64;     // deferred clocks per map (crdt_map_mvreg_merge's per-side limit)
-constexpr uint32_t kNestMax = 256;   // members / deferred clocks per nested set or map (crdt_map_orswot_merge's)
+constexpr uint32_t kRowMax = kMapActorsMax;  // dense rows up to this many actors are built in LDS
+constexpr uint32_t kDefMax = kMapMvregDcap;  // deferred clocks per map (Map<u64, MVReg>, the nested map's two levels)
+constexpr uint32_t kNestMax = kMapOrswotMcap;  // members / deferred clocks per nested set or map (Map<u64, Orswot>)
+static_assert(kMapMapDcap <= kDefMax, "one table holds an outer map's deferred clocks");
+static_assert(kMapOrswotVdcap <= kNestMax && kMapOrswotDcap <= kNestMax, "one table holds either deferred list");
 
 // One wave's LDS: the blob window, the dense row under construction (all zero
 // between two clocks) and the deferred clocks' positions, sizes and ranks.
@@ -1135,9 +1139,7 @@ __global__ __launch_bounds__(kW* kWaves) void nested_bincode_egest_kernel(
 }
 
 uint32_t grid_for(uint64_t n_obj, uint32_t blocks_per_cu) {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const uint64_t want = (n_obj + kWaves - 1u) / kWaves, cap = (uint64_t)cus * blocks_per_cu;
+  const uint64_t want = (n_obj + kWaves - 1u) / kWaves, cap = (uint64_t)cu_count() * blocks_per_cu;
   return (uint32_t)(want < cap ? want : cap);
 }
 

@@ -26,6 +26,7 @@
 
 #include "../../include/crdts_hip.h"
 #include "kernels.h"
+#include "map_limits.h"
 #include "map_rows.h"
 #include "sched.h"
 
@@ -35,7 +36,8 @@ namespace {
 using namespace maprow;
 
 constexpr uint32_t kMmW = 64;
-constexpr uint32_t kMmComb = 128;  // combined outer deferred entries (<= dcap_self + dcap_other, dcap <= 64)
+constexpr uint32_t kMmComb = 2u * kMapMapDcap;  // combined outer deferred entries (<= dcap_self + dcap_other)
+static_assert(kMapMapDcap <= 64u, "lane d holds outer deferred entry d's set size");
 constexpr uint32_t kMmStage = 128;  // u64: the map deferred sets staged per object when both sides fit
 constexpr uint64_t kMmNone = ~0ull;
 
@@ -60,7 +62,7 @@ __global__ __launch_bounds__(kMmW) void map_map_outer_kernel(crdt_map_map_slab S
                                                              int* __restrict__ status, uint32_t* __restrict__ ctl) {
   __shared__ uint32_t comb[kMmComb];  // (self deferred idx + 1) | (other deferred idx + 1) << 8
   __shared__ uint64_t md[kMmStage];    // the object's map deferred sets, used entries (when they fit)
-  __shared__ uint32_t mdn[2][64];      // their sizes (dcap <= 64), self / other
+  __shared__ uint32_t mdn[2][kMapMapDcap];  // their sizes, self / other
   const uint32_t lane = threadIdx.x;
   BlockTickets<4> sched(n_obj, ctl + 3, lane);  // (sched.h)
   for (uint64_t i = sched.first(); i < n_obj; i = sched.next(i)) {
@@ -73,7 +75,7 @@ __global__ __launch_bounds__(kMmW) void map_map_outer_kernel(crdt_map_map_slab S
     if (nS > S.kcap || nO > O.kcap || dS > S.dcap || dO > O.dcap) {
       if (lane == 0u) atomicCAS(status, 0, CRDT_ENONCANON);
     } else {
-      // lane k: key k (k < 64) and map deferred entry k's set size (dcap <= 64)
+      // lane k: key k (k < 64) and map deferred entry k's set size (dcap <= kMapMapDcap)
       const uint64_t kregS = lane < nS ? S.keys[i * S.kcap + lane] : 0ull;
       const uint64_t kregO = lane < nO ? O.keys[i * O.kcap + lane] : 0ull;
       const uint32_t dnS = lane < dS ? S.dset_n[i * S.dcap + lane] : 0u, dnO = lane < dO ? O.dset_n[i * O.dcap + lane] : 0u;
@@ -243,9 +245,7 @@ int launch_map_map_merge(const crdt_map_map_slab& S, const crdt_map_map_slab& O,
   uint64_t* tsrc = (uint64_t*)take(16ull * nt);
   uint64_t* Tb = (uint64_t*)take(8ull * nt * A);
   if (hipMemsetAsync(ctl, 0, 4 * sizeof(uint32_t), stream) != hipSuccess) return CRDT_EHIP;  // ctl[3]: tickets
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const uint64_t cap = (uint64_t)cus * 28u;
+  const uint64_t cap = (uint64_t)cu_count() * 28u;
   const uint32_t blocks = (uint32_t)(n_obj < cap ? n_obj : cap);
   if (A > 64u)
     hipLaunchKernelGGL((map_map_outer_kernel<2>), dim3(blocks), dim3(kMmW), 0, stream, S, O, R, n_obj, A, tsrc, Tb,

@@ -23,17 +23,21 @@
 //      self, or a physical slot of a scratch inner slab laid out like out's
 //      (row i * kcap + p). An inner map is copied (used slots) into a free
 //      physical slot on its first edit or truncation and edited there in place
-//      (map_mvreg_ws.h); a dropped entry frees its slot. The sources of the
+//      (map_mvreg_ws.h, map_wave.h); a dropped entry frees its slot. The sources of the
 //      final keys are the tasks of (2).
 //  (2) the placement, one wave per out key slot: the source's used slots to
 //      inner row i * kcap + k of out. Inner maps no op touched go self -> out
 //      here and never pass through (1).
 // The op headers, and the clock pairs of the first ops, are staged in LDS 64
-// ops at a time (map_apply.hip).
+// ops at a time. This kernel keeps its own copy of map_ops.h's reader, with the
+// inner op's dot and key beside the header: through the shared reader its
+// registers and scratch were the same and it measured 0.4 % slower (DESIGN.md
+// §5p). A change to the staging window in map_ops.h is made here as well.
 #include <hip/hip_runtime.h>
 
 #include "../../include/crdts_hip.h"
 #include "kernels.h"
+#include "map_limits.h"
 #include "map_mvreg_ws.h"
 #include "map_rows.h"
 #include "sched.h"
@@ -44,6 +48,7 @@ namespace {
 using namespace maprow;
 using namespace mapws;
 
+static_assert(kMapMapDcap <= kW, "lane d holds outer deferred entry d's set size");
 constexpr uint64_t kSrcNone = ~0ull;      // an unused out key slot: no task
 constexpr uint64_t kSrcWork = 1ull << 63;  // | p: physical slot p of the object's scratch rows (else: a self inner row)
 
@@ -71,18 +76,13 @@ __global__ __launch_bounds__(kW, NS == 1 ? 6 : 1) void map_map_apply_kernel(crdt
     const uint64_t lo = i ? uni64(P.obj_end[i - 1u]) : 0ull, hi = uni64(P.obj_end[i]);
     if (nS > S.kcap || dS > S.dcap || lo > hi || hi > (uint64_t)P.n_ops) err = CRDT_ENONCANON;
     if (!err) {
-      const uint32_t dnS = lane < dS ? S.dset_n[i * S.dcap + lane] : 0u;  // (dcap <= 64: api.hip)
+      const uint32_t dnS = lane < dS ? S.dset_n[i * S.dcap + lane] : 0u;  // (dcap <= kMapMapDcap)
       if (__ballot(dnS > S.scap) != 0ull) err = CRDT_ENONCANON;
       if (!err) {
         // ---- out[i]'s outer arrays; self[i]'s used slots copied in (out caps >= self's)
         uint64_t* const keys = R.keys + i * Rk;
         uint64_t* const ecl = R.eclock + i * Rk * A;
-        DefRef def;
-        def.dcl = R.dclock + i * R.dcap * A;
-        def.dsn = R.dset_n + i * R.dcap;
-        def.dse = R.dset + i * R.dcap * R.scap;
-        def.Rd = R.dcap;
-        def.Rs = R.scap;
+        const DefRef def = def_ref(R, i, A);
         copy_n(keys, S.keys + i * S.kcap, nS, lane);
         copy_n(ecl, S.eclock + i * S.kcap * A, nS * A, lane);
         for (uint32_t k = lane; k < nS; k += kW) tsrc[k] = i * S.kcap + k;
@@ -392,9 +392,7 @@ int launch_map_map_apply(const crdt_map_map_slab& S, const crdt_map_map_ops& P, 
   uint32_t* fre = nullptr;
   const crdt_map_mvreg_slab W = carve(scratch, R, n_obj, A, &src, &fre, nullptr);
   if (hipMemsetAsync(ctl, 0, 4 * sizeof(uint32_t), stream) != hipSuccess) return CRDT_EHIP;  // ctl[3]: tickets
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const uint64_t cap = (uint64_t)cus * 28u;
+  const uint64_t cap = (uint64_t)cu_count() * 28u;
   uint32_t blocks = (uint32_t)(n_obj < cap ? n_obj : cap);
   if (A > 64u)  // 65-128 actors: two slots per lane
     hipLaunchKernelGGL((map_map_apply_kernel<2>), dim3(blocks), dim3(kW), 0, stream, S, P, R, W, src, fre, n_obj, A,
@@ -403,15 +401,8 @@ int launch_map_map_apply(const crdt_map_map_slab& S, const crdt_map_map_ops& P, 
     hipLaunchKernelGGL((map_map_apply_kernel<1>), dim3(blocks), dim3(kW), 0, stream, S, P, R, W, src, fre, n_obj, A,
                        status, ctl);
   if (hipGetLastError() != hipSuccess) return CRDT_EHIP;
-  // the kept keys are an object's first slots: a grid stride coprime with the
-  // slots per object spreads them over every block (map.hip)
   const uint64_t nt = n_obj * R.kcap;
-  blocks = (uint32_t)(nt < cap ? nt : cap);
-  auto gcd = [](uint32_t a, uint32_t b) {
-    while (b) { const uint32_t t = a % b; a = b; b = t; }
-    return a;
-  };
-  while (blocks > 1u && R.kcap > 1u && gcd(blocks, R.kcap) != 1u) --blocks;
+  blocks = coprime_grid((uint32_t)(nt < cap ? nt : cap), R.kcap);  // (sched.h)
   hipLaunchKernelGGL(map_map_place_kernel, dim3(blocks), dim3(kW), 0, stream, S.inner, W, R.inner, src, nt, R.kcap, A,
                      status);
   return hipGetLastError() == hipSuccess ? CRDT_OK : CRDT_EHIP;

@@ -42,7 +42,7 @@ constexpr uint32_t kMoStageMax = 16384;  // map deferred staging area limit per 
 
 __device__ __forceinline__ bool set_has(const uint64_t* set, uint32_t n, uint64_t key, uint32_t lane) {
   bool f = false;
-  for (uint32_t j = lane; j < n; j += kMoW) f = f || set[j] == key;
+  for (uint32_t j = lane; j < n; j += kW) f = f || set[j] == key;
   return __ballot(f) != 0ull;
 }
 
@@ -52,12 +52,12 @@ typedef uint64_t mo_u64x2 __attribute__((ext_vector_type(2)));
 template <class F>
 __device__ __forceinline__ void fill64(uint64_t* dst, uint64_t n, uint32_t lane, F at) {
   if ((((uintptr_t)dst) & 15u) == 0u && (n & 1u) == 0u) {
-    for (uint64_t p = lane; p < n / 2u; p += kMoW) {
+    for (uint64_t p = lane; p < n / 2u; p += kW) {
       const mo_u64x2 v = {at(2u * p), at(2u * p + 1u)};
       __builtin_nontemporal_store(v, (mo_u64x2*)(dst + 2u * p));
     }
   } else {
-    for (uint64_t e = lane; e < n; e += kMoW) dst[e] = at(e);
+    for (uint64_t e = lane; e < n; e += kW) dst[e] = at(e);
   }
 }
 
@@ -66,20 +66,20 @@ __device__ __forceinline__ void fill64(uint64_t* dst, uint64_t n, uint32_t lane,
 // the key walk's registers), then every array (ws_copy: each load
 // independent of the others' results — the deferred sets copied
 // capacity-strided, their sizes by one lane each — so both sides' slots cost
-// one round trip), then the caller's mo_sync.
+// one round trip), then the caller's mw_sync.
 __device__ __forceinline__ void ws_counts(Ws& W, const crdt_map_orswot_slab& X, uint64_t ki, uint32_t k, uint32_t vm,
                                           uint32_t vd) {
   // key k's counts: lane k of the registers the key walk loaded (k < 64)
-  W.nm = k < kMoW ? (uint32_t)__builtin_amdgcn_readlane(vm, k) : uni(X.vn_mem[ki]);
-  W.nd = k < kMoW ? (uint32_t)__builtin_amdgcn_readlane(vd, k) : uni(X.vn_def[ki]);
+  W.nm = k < kW ? (uint32_t)__builtin_amdgcn_readlane(vm, k) : uni32(X.vn_mem[ki]);
+  W.nd = k < kW ? (uint32_t)__builtin_amdgcn_readlane(vd, k) : uni32(X.vn_def[ki]);
 }
 __device__ void ws_copy(Ws& W, const crdt_map_orswot_slab& X, uint64_t ki, const Caps& c, uint32_t lane) {
-  for (uint32_t j = lane; j < W.nm; j += kMoW) W.key[j] = X.vmem[ki * X.mcap + j];
-  for (uint32_t e = lane; e < W.nm * c.A; e += kMoW) W.row[e] = X.vmclock[ki * X.mcap * c.A + e];
-  for (uint32_t e = lane; e < W.nd * c.A; e += kMoW) W.dclk[e] = X.vdclock[ki * X.vdcap * c.A + e];
-  for (uint32_t d = lane; d < W.nd; d += kMoW) W.dn[d] = X.vdset_n[ki * X.vdcap + d];
+  for (uint32_t j = lane; j < W.nm; j += kW) W.key[j] = X.vmem[ki * X.mcap + j];
+  for (uint32_t e = lane; e < W.nm * c.A; e += kW) W.row[e] = X.vmclock[ki * X.mcap * c.A + e];
+  for (uint32_t e = lane; e < W.nd * c.A; e += kW) W.dclk[e] = X.vdclock[ki * X.vdcap * c.A + e];
+  for (uint32_t d = lane; d < W.nd; d += kW) W.dn[d] = X.vdset_n[ki * X.vdcap + d];
   const uint32_t vs = X.vscap;
-  for (uint32_t e = lane; e < W.nd * vs; e += kMoW) {  // capacity-strided: no wait for the sizes
+  for (uint32_t e = lane; e < W.nd * vs; e += kW) {  // capacity-strided: no wait for the sizes
     const uint32_t d = e / vs;
     W.dset[d * W.sw + (e - d * vs)] = X.vdset[ki * X.vdcap * vs + e];
   }
@@ -153,7 +153,7 @@ __device__ void ws_merge(const Ws& Wc, const Ws& Wo, Ws& Wn, Row<NS>& sclk, Row<
   }
   Wn.nd = nd;
   sclk = vmax(sclk, oclk);  // :153
-  mo_sync();
+  mw_sync();
   ws_apply_deferred(Wn, sclk, mdead, ddead, c, lane);  // :155
 }
 
@@ -162,7 +162,7 @@ template <int NS>
 __device__ bool ws_store(const Ws& W, Row<NS> clk, const crdt_map_orswot_slab& R, uint64_t kr, const Caps& c,
                          uint32_t lane) {
   bool fits = W.nm <= R.mcap && W.nd <= R.vdcap;
-  for (uint32_t d = 0; d < W.nd; ++d) fits = fits && uni(W.dn[d]) <= R.vscap;
+  for (uint32_t d = 0; d < W.nd; ++d) fits = fits && uni32(W.dn[d]) <= R.vscap;
   if (!fits) return false;
   strow(R.vclock + kr * c.A, clk, c.A, lane);
   if (lane == 0u) { R.vn_mem[kr] = W.nm; R.vn_def[kr] = W.nd; }
@@ -177,14 +177,14 @@ __device__ bool ws_store(const Ws& W, Row<NS> clk, const crdt_map_orswot_slab& R
   fill64(R.vmem + kr * R.mcap, nm, lane, [&](uint64_t j) { return key[j]; });
   fill64(R.vmclock + kr * R.mcap * c.A, nmA, lane, [&](uint64_t e) { return row[e]; });
   fill64(R.vdclock + kr * R.vdcap * c.A, ndA, lane, [&](uint64_t e) { return dclk[e]; });
-  for (uint32_t d = lane; d < nd; d += kMoW) R.vdset_n[kr * R.vdcap + d] = dn[d];
+  for (uint32_t d = lane; d < nd; d += kW) R.vdset_n[kr * R.vdcap + d] = dn[d];
   for (uint32_t d = 0; d < nd; ++d)
-    fill64(R.vdset + (kr * R.vdcap + d) * vs, uni(dn[d]), lane, [&](uint64_t j) { return dset[d * SW + j]; });
+    fill64(R.vdset + (kr * R.vdcap + d) * vs, uni32(dn[d]), lane, [&](uint64_t j) { return dset[d * SW + j]; });
   return true;
 }
 
 template <int NS, int MINW = 4>
-__global__ __launch_bounds__(kMoW, MINW) void map_orswot_merge_kernel(crdt_map_orswot_slab S, crdt_map_orswot_slab O,
+__global__ __launch_bounds__(kW, MINW) void map_orswot_merge_kernel(crdt_map_orswot_slab S, crdt_map_orswot_slab O,
                                                                 crdt_map_orswot_slab R, uint64_t n_obj, uint32_t A,
                                                                 uint32_t md_cap, int* __restrict__ status,
                                                                 uint32_t* __restrict__ ctl) {
@@ -210,7 +210,7 @@ __global__ __launch_bounds__(kMoW, MINW) void map_orswot_merge_kernel(crdt_map_o
     carve(W1, c.MW, c.DW, c.SW);
     carve(W2, O.mcap, O.vdcap, O.vscap);
     mdead = (uint32_t*)p;
-    for (uint32_t j = lane; j < c.MW + c.DW; j += kMoW) mdead[j] = 0u;
+    for (uint32_t j = lane; j < c.MW + c.DW; j += kW) mdead[j] = 0u;
     md = p + (c.MW + c.DW + 1u) / 2u;
   }
   // the map deferred bookkeeping (dcap_s + dcap_o <= 512 entries each, after
@@ -226,13 +226,13 @@ __global__ __launch_bounds__(kMoW, MINW) void map_orswot_merge_kernel(crdt_map_o
   W1.dn = W0.dn + S.vdcap;
   W2.dn = W1.dn + c.DW;
   uint32_t* const ddead = mdead + c.MW;
-  mo_sync();
+  mw_sync();
   BlockTickets<4> sched(n_obj, ctl + 3, lane);  // (sched.h)
   for (uint64_t i = sched.first(); i < n_obj; i = sched.next(i)) {
     const Row<NS> cS = rowv<NS>(S.clock, i, A, lane), cO = rowv<NS>(O.clock, i, A, lane);
     const Row<NS> cM = vmax(cS, cO);  // VClock::merge
-    const uint32_t nS = uni(S.n_keys[i]), nO = uni(O.n_keys[i]);
-    const uint32_t dS = uni(S.n_def[i]), dO = uni(O.n_def[i]);
+    const uint32_t nS = uni32(S.n_keys[i]), nO = uni32(O.n_keys[i]);
+    const uint32_t dS = uni32(S.n_def[i]), dO = uni32(O.n_def[i]);
     if (nS > S.kcap || nO > O.kcap || dS > S.dcap || dO > O.dcap) {
       if (lane == 0u) atomicCAS(status, 0, CRDT_ENONCANON);
       continue;
@@ -251,31 +251,31 @@ __global__ __launch_bounds__(kMoW, MINW) void map_orswot_merge_kernel(crdt_map_o
                                                                                    : (vdO < O.vdcap ? vdO : O.vdcap);
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) {
-      const uint32_t t = __shfl_xor(mvd, off, kMoW);
+      const uint32_t t = __shfl_xor(mvd, off, kW);
       mvd = t > mvd ? t : mvd;
     }
-    mvd = uni(mvd);
+    mvd = uni32(mvd);
     for (uint32_t d = 0; d < mvd; ++d) {
       if (ls && d < vdS) bad = bad || S.vdset_n[(i * S.kcap + lane) * S.vdcap + d] > S.vscap;
       if (lo && d < vdO) bad = bad || O.vdset_n[(i * O.kcap + lane) * O.vdcap + d] > O.vscap;
     }
-    for (uint32_t k = kMoW + lane; k < nS; k += kMoW) {
+    for (uint32_t k = kW + lane; k < nS; k += kW) {
       const uint64_t ki = i * S.kcap + k;
       bad = bad || S.vn_mem[ki] > S.mcap || S.vn_def[ki] > S.vdcap;
       for (uint32_t d = 0; !bad && d < S.vn_def[ki]; ++d) bad = S.vdset_n[ki * S.vdcap + d] > S.vscap;
     }
-    for (uint32_t k = kMoW + lane; k < nO; k += kMoW) {
+    for (uint32_t k = kW + lane; k < nO; k += kW) {
       const uint64_t ki = i * O.kcap + k;
       bad = bad || O.vn_mem[ki] > O.mcap || O.vn_def[ki] > O.vdcap;
       for (uint32_t d = 0; !bad && d < O.vn_def[ki]; ++d) bad = O.vdset_n[ki * O.vdcap + d] > O.vscap;
     }
     // the map deferred set sizes, one lane per entry
-    for (uint32_t d = lane; d < dS; d += kMoW) {
+    for (uint32_t d = lane; d < dS; d += kW) {
       const uint32_t x = S.dset_n[i * S.dcap + d];
       mdn0[d] = x;
       bad = bad || x > S.scap;
     }
-    for (uint32_t d = lane; d < dO; d += kMoW) {
+    for (uint32_t d = lane; d < dO; d += kW) {
       const uint32_t x = O.dset_n[i * O.dcap + d];
       mdn1[d] = x;
       bad = bad || x > O.scap;
@@ -284,7 +284,7 @@ __global__ __launch_bounds__(kMoW, MINW) void map_orswot_merge_kernel(crdt_map_o
       if (lane == 0u) atomicCAS(status, 0, CRDT_ENONCANON);
       continue;
     }
-    mo_sync();
+    mw_sync();
     // the map deferred sets staged in LDS when they fit (md_cap words): the
     // key loop asks each of them about every key. (Staging their clocks too
     // cost more occupancy than the round trips it saved: DESIGN.md §9.)
@@ -293,16 +293,16 @@ __global__ __launch_bounds__(kMoW, MINW) void map_orswot_merge_kernel(crdt_map_o
     uint64_t* const mdS = md;
     uint64_t* const mdO = mdS + dS * sS;
     if (st) {  // the used entries of each set
-      for (uint32_t e = lane; e < dS * sS; e += kMoW) {
+      for (uint32_t e = lane; e < dS * sS; e += kW) {
         const uint32_t d = e / sS;
         if (e - d * sS < mdn0[d]) mdS[e] = S.dset[i * S.dcap * sS + e];
       }
-      for (uint32_t e = lane; e < dO * sO; e += kMoW) {
+      for (uint32_t e = lane; e < dO * sO; e += kW) {
         const uint32_t d = e / sO;
         if (e - d * sO < mdn1[d]) mdO[e] = O.dset[i * O.dcap * sO + e];
       }
     }
-    mo_sync();
+    mw_sync();
     auto sdc = [&](uint32_t a) -> Row<NS> { return rowv<NS>(S.dclock, i * S.dcap + a, A, lane); };
     auto odc = [&](uint32_t b) -> Row<NS> { return rowv<NS>(O.dclock, i * O.dcap + b, A, lane); };
     // ---- combined map deferred list: self's, plus other's that self's clock does not cover
@@ -322,7 +322,7 @@ __global__ __launch_bounds__(kMoW, MINW) void map_orswot_merge_kernel(crdt_map_o
         if (o >= 0) ++b;
       }
     }
-    mo_sync();
+    mw_sync();
     auto comb_clock = [&](uint32_t e) -> Row<NS> {
       const uint32_t sa = e & 0xFFFFu, sb = e >> 16;
       return sa ? sdc(sa - 1u) : odc(sb - 1u);
@@ -331,26 +331,26 @@ __global__ __launch_bounds__(kMoW, MINW) void map_orswot_merge_kernel(crdt_map_o
     auto comb_named = [&](uint64_t key) -> uint32_t {
       uint32_t nn = 0;
       for (uint32_t k = 0; k < nc; ++k) {
-        const uint32_t e = uni(comb[k]), sa = e & 0xFFFFu, sb = e >> 16;
+        const uint32_t e = uni32(comb[k]), sa = e & 0xFFFFu, sb = e >> 16;
         bool f = false;
         if (sa)
-          f = set_has(st ? mdS + (sa - 1u) * sS : S.dset + (i * S.dcap + sa - 1u) * sS, uni(mdn0[sa - 1u]), key, lane);
+          f = set_has(st ? mdS + (sa - 1u) * sS : S.dset + (i * S.dcap + sa - 1u) * sS, uni32(mdn0[sa - 1u]), key, lane);
         if (!f && sb)
-          f = set_has(st ? mdO + (sb - 1u) * sO : O.dset + (i * O.dcap + sb - 1u) * sO, uni(mdn1[sb - 1u]), key, lane);
+          f = set_has(st ? mdO + (sb - 1u) * sO : O.dset + (i * O.dcap + sb - 1u) * sO, uni32(mdn1[sb - 1u]), key, lane);
         if (f) {
           if (lane == 0u) nl[nn] = k;
           ++nn;
         }
       }
-      mo_sync();
+      mw_sync();
       return nn;
     };
     // ---- entries, key by key in ascending order
     uint32_t nk = 0, a = 0, b = 0;
     bool over = false;
     while (a < nS || b < nO) {
-      const uint64_t ka = a < nS ? (a < kMoW ? lane64(kregS, a) : uni64(S.keys[i * S.kcap + a])) : ~0ull;
-      const uint64_t kb = b < nO ? (b < kMoW ? lane64(kregO, b) : uni64(O.keys[i * O.kcap + b])) : ~0ull;
+      const uint64_t ka = a < nS ? (a < kW ? lane64(kregS, a) : uni64(S.keys[i * S.kcap + a])) : ~0ull;
+      const uint64_t kb = b < nO ? (b < kW ? lane64(kregO, b) : uni64(O.keys[i * O.kcap + b])) : ~0ull;
       const bool chs = a < nS && (b >= nO || ka <= kb), cho = b < nO && (a >= nS || kb <= ka);
       const uint64_t ckey = chs ? ka : kb;
       const uint64_t ia = i * S.kcap + a, ib = i * O.kcap + b;
@@ -380,7 +380,7 @@ __global__ __launch_bounds__(kMoW, MINW) void map_orswot_merge_kernel(crdt_map_o
       // (subtracts commute; an entry emptied at any step is gone for good)
       const uint32_t nn = keep && nc ? comb_named(ckey) : 0u;
       if (keep) {
-        for (uint32_t t = 0; t < nn; ++t) ec = vsub(ec, comb_clock(uni(comb[uni(nl[t])])));
+        for (uint32_t t = 0; t < nn; ++t) ec = vsub(ec, comb_clock(uni32(comb[uni32(nl[t])])));
         keep = vany(ec);
       }
       if (keep && nk >= R.kcap) {
@@ -393,7 +393,7 @@ __global__ __launch_bounds__(kMoW, MINW) void map_orswot_merge_kernel(crdt_map_o
         if (cho) ws_counts(W2, O, ib, cb, vmO, vdO);
         if (chs) ws_copy(W0, S, ia, c, lane);
         if (cho) ws_copy(W2, O, ib, c, lane);
-        mo_sync();
+        mw_sync();
         Row<NS> vclk = chs ? vS : vO;
         Ws Wk = chs ? W0 : W2;
         if (chs && cho) {
@@ -404,7 +404,7 @@ __global__ __launch_bounds__(kMoW, MINW) void map_orswot_merge_kernel(crdt_map_o
         // clock naming the key, in CLOCK ORDER (apply_deferred -> apply_rm)
         ws_truncate(Wk, vclk, del, mdead, ddead, c, lane);
         for (uint32_t t = 0; t < nn; ++t)
-          ws_truncate(Wk, vclk, comb_clock(uni(comb[uni(nl[t])])), mdead, ddead, c, lane);
+          ws_truncate(Wk, vclk, comb_clock(uni32(comb[uni32(nl[t])])), mdead, ddead, c, lane);
         const uint64_t ir = i * R.kcap + nk;
         if (ws_store(Wk, vclk, R, ir, c, lane)) {
           if (lane == 0u) R.keys[ir] = ckey;
@@ -413,7 +413,7 @@ __global__ __launch_bounds__(kMoW, MINW) void map_orswot_merge_kernel(crdt_map_o
         } else {
           over = true;
         }
-        mo_sync();
+        mw_sync();
       }
     }
     if (lane == 0u) R.n_keys[i] = nk;
@@ -421,7 +421,7 @@ __global__ __launch_bounds__(kMoW, MINW) void map_orswot_merge_kernel(crdt_map_o
     // ---- map deferred kept: the combined clocks the merged clock does not cover, sets united
     uint32_t nd = 0;
     for (uint32_t k = 0; k < nc; ++k) {
-      const uint32_t e = uni(comb[k]);
+      const uint32_t e = uni32(comb[k]);
       const uint32_t sa = e & 0xFFFFu, sb = e >> 16;
       const Row<NS> D = comb_clock(e);
       if (vle(D, cM)) continue;
@@ -444,12 +444,12 @@ __global__ __launch_bounds__(kMoW, MINW) void map_orswot_merge_kernel(crdt_map_o
         }
         R.dset_n[dr] = cnt < R.scap ? cnt : R.scap;
       }
-      over = over || uni(cnt) > R.scap;
+      over = over || uni32(cnt) > R.scap;
       ++nd;
     }
     if (lane == 0u) R.n_def[i] = nd;
     if (over && lane == 0u) atomicCAS(status, 0, CRDT_ECAPACITY);
-    mo_sync();
+    mw_sync();
   }
 }
 
@@ -482,15 +482,14 @@ int launch_map_orswot_merge(const crdt_map_orswot_slab& S, const crdt_map_orswot
   const void* fn = A > 64u ? (const void*)map_orswot_merge_kernel<2>
                    : variant == 402 ? (const void*)map_orswot_merge_kernel<1, 1>
                                     : (const void*)map_orswot_merge_kernel<1>;
-  int dev = 0, cus = 256, occ = 0;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  int occ = 0;
   // one single-wave block per resident slot (LDS-bound: the workspace sizes it)
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, kMoW, lds + md_bytes) != hipSuccess || occ < 1) occ = 16;
-  const uint64_t cap = (uint64_t)cus * (uint32_t)occ;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, kW, lds + md_bytes) != hipSuccess || occ < 1) occ = 16;
+  const uint64_t cap = (uint64_t)cu_count() * (uint32_t)occ;
   const uint32_t blocks = (uint32_t)(n_obj < cap ? n_obj : cap);
   if (hipMemsetAsync(ctl, 0, 4 * sizeof(uint32_t), stream) != hipSuccess) return CRDT_EHIP;  // ctl[3]: tickets
   void* args[] = {(void*)&S, (void*)&O, (void*)&R, &n_obj, &A, (void*)&md_cap, &status, &ctl};
-  if (hipLaunchKernel(fn, dim3(blocks), dim3(kMoW), args, lds + md_bytes, stream) != hipSuccess) return CRDT_EHIP;
+  if (hipLaunchKernel(fn, dim3(blocks), dim3(kW), args, lds + md_bytes, stream) != hipSuccess) return CRDT_EHIP;
   return hipGetLastError() == hipSuccess ? CRDT_OK : CRDT_EHIP;
 }
 

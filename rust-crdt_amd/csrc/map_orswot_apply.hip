@@ -14,7 +14,8 @@
 //
 // One wave per object; lane = actor slot (map_rows.h). self[i]'s used slots
 // are copied into out[i]. The key-level arrays and the map's deferred removes
-// are then edited in out[i] in place, as map_apply.hip does; the nested set an
+// are then edited in out[i] in place, as map_apply.hip does (the edits'
+// helpers: map_wave.h); the nested set an
 // op works on is staged in an LDS workspace (map_orswot_ws.h: members, member
 // clocks, deferred clocks and their sets, with the entry clock and the set's
 // top clock in registers), edited there, and written back only when another
@@ -23,12 +24,13 @@
 // starts in the workspace and is never read from HBM. Up to 64 keys are
 // mirrored in LDS, so the search every op starts with reads no HBM. Every
 // cross-lane edit of out[i] or of the workspace ends in a wave-local fence +
-// barrier. The op headers, and the clock pairs of the first ops, are staged in
-// LDS 64 ops at a time.
+// barrier. The ops are read through map_ops.h: headers, and the clock pairs
+// of the first ops, staged in LDS 64 ops at a time.
 #include <hip/hip_runtime.h>
 
 #include "../../include/crdts_hip.h"
 #include "kernels.h"
+#include "map_ops.h"
 #include "map_orswot_ws.h"
 #include "map_rows.h"
 #include "sched.h"
@@ -41,66 +43,15 @@ using namespace mows;
 constexpr uint32_t kOaLdsMax = kMapOrswotApplyLdsMax;  // dynamic workspace limit per wave (kernels.h)
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 
-// a count only lane 0 ever writes
-__device__ __forceinline__ uint32_t cnt0(const uint32_t* p, uint32_t lane) {
-  uint32_t x = 0u;
-  if (lane == 0u) x = *p;
-  return uni(x);
-}
-template <class T>
-__device__ __forceinline__ void copy_n(T* dst, const T* src, uint32_t n, uint32_t lane) {
-  for (uint32_t e = lane; e < n; e += kMoW) dst[e] = src[e];
-}
-// a[k + 1] = a[k] for k in [p, n), the last 64 first; a[k - 1] = a[k] for k in
-// (p, n), the first 64 first: a chunk's loads are all done before its stores
-__device__ void shift_up(uint64_t* a, uint32_t p, uint32_t n, uint32_t lane) {
-  for (uint32_t hi = n; hi > p;) {
-    const uint32_t lo = hi - p > kMoW ? hi - kMoW : p;
-    const uint32_t k = lo + lane;
-    uint64_t x = 0ull;
-    if (k < hi) x = a[k];
-    mo_sync();
-    if (k < hi) a[k + 1u] = x;
-    mo_sync();
-    hi = lo;
-  }
-}
-__device__ void shift_down(uint64_t* a, uint32_t p, uint32_t n, uint32_t lane) {
-  for (uint32_t lo = p + 1u; lo < n; lo += kMoW) {
-    const uint32_t k = lo + lane;
-    uint64_t x = 0ull;
-    if (k < n) x = a[k];
-    mo_sync();
-    if (k < n) a[k - 1u] = x;
-    mo_sync();
-  }
-}
-// `key` in the ascending a[0, n): pos = how many are below it; is it there?
-__device__ bool find_key(const uint64_t* a, uint32_t n, uint64_t key, uint32_t lane, uint32_t& pos) {
-  uint32_t below = 0u;
-  bool hit = false;
-  for (uint32_t b = 0u; b < n; b += kMoW) {
-    const uint32_t k = b + lane;
-    const uint64_t x = k < n ? a[k] : ~0ull;
-    below += (uint32_t)__popcll(__ballot(k < n && x < key));
-    hit = hit || __ballot(k < n && x == key) != 0ull;
-  }
-  pos = below;
-  return hit;
-}
-
 // (5 waves/SIMD at one slot per lane: bounded to 96 VGPRs the kernel keeps
 // 40 B/lane in scratch and is faster than at 4 or 6 waves/SIMD — DESIGN.md §5i)
 template <int NS>
-__global__ __launch_bounds__(kMoW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel(
+__global__ __launch_bounds__(kW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel(
     crdt_map_orswot_slab S, crdt_map_orswot_ops P, crdt_map_orswot_slab R, uint64_t n_obj, uint32_t A,
     int* __restrict__ status, uint32_t* __restrict__ ctl) {
   extern __shared__ uint64_t oa_lds[];
-  __shared__ uint64_t oc[128];  // the op's clock, scattered to a dense row
-  // a chunk of 64 op headers and the first 64 clock pairs of its ops
-  __shared__ uint32_t hkind[kMoW], hact[kMoW], pact[kMoW];
-  __shared__ uint64_t hkey[kMoW], hctr[kMoW], hmem[kMoW], hend[kMoW], pctr[kMoW];
-  __shared__ uint64_t lk[kMoW];  // a copy of out[i]'s keys while there are at most 64 (kvalid)
+  const mapops::OpStage ops = mapops::op_stage();  // the op reader's LDS stage (map_ops.h)
+  __shared__ uint64_t lk[kW];  // a copy of out[i]'s keys while there are at most 64 (kvalid)
   const uint32_t lane = threadIdx.x;
   const uint64_t Rk = R.kcap, Rm = R.mcap, Rv = R.vdcap, Rvs = R.vscap, Rd = R.dcap, Rs = R.scap;
   const Caps c{R.mcap, R.vdcap, R.vscap, A};
@@ -116,12 +67,12 @@ __global__ __launch_bounds__(kMoW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel
   W.nm = W.nd = 0u;
   uint32_t* const ddead = W.dn + Rv;
   uint32_t* const mdead = ddead + Rv;
-  for (uint32_t j = lane; j < R.vdcap + R.mcap; j += kMoW) ddead[j] = 0u;
-  mo_sync();
+  for (uint32_t j = lane; j < R.vdcap + R.mcap; j += kW) ddead[j] = 0u;
+  mw_sync();
   BlockTickets<4> sched(n_obj, ctl + 3, lane);
   for (uint64_t i = sched.first(); i < n_obj; i = sched.next(i)) {
     // ---- the input row, checked as the merge checks it (map_orswot.hip)
-    const uint32_t nS = uni(S.n_keys[i]), dS = uni(S.n_def[i]);
+    const uint32_t nS = uni32(S.n_keys[i]), dS = uni32(S.n_def[i]);
     const uint64_t lo = i ? uni64(P.obj_end[i - 1u]) : 0ull, hi = uni64(P.obj_end[i]);
     if (nS > S.kcap || dS > S.dcap || lo > hi || hi > (uint64_t)P.n_ops) {
       if (lane == 0u) atomicCAS(status, 0, CRDT_ENONCANON);
@@ -131,17 +82,17 @@ __global__ __launch_bounds__(kMoW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel
     const uint32_t vmS = ls ? S.vn_mem[i * S.kcap + lane] : 0u, vdS = ls ? S.vn_def[i * S.kcap + lane] : 0u;
     bool bad = vmS > S.mcap || vdS > S.vdcap;
     for (uint32_t d = 0; !bad && d < vdS; ++d) bad = S.vdset_n[(i * S.kcap + lane) * S.vdcap + d] > S.vscap;
-    for (uint32_t k = kMoW + lane; k < nS; k += kMoW) {
+    for (uint32_t k = kW + lane; k < nS; k += kW) {
       const uint64_t ki = i * S.kcap + k;
       bad = bad || S.vn_mem[ki] > S.mcap || S.vn_def[ki] > S.vdcap;
       for (uint32_t d = 0; !bad && d < S.vn_def[ki]; ++d) bad = S.vdset_n[ki * S.vdcap + d] > S.vscap;
     }
-    for (uint32_t d = lane; d < dS; d += kMoW) bad = bad || S.dset_n[i * S.dcap + d] > S.scap;
+    for (uint32_t d = lane; d < dS; d += kW) bad = bad || S.dset_n[i * S.dcap + d] > S.scap;
     if (__ballot(bad) != 0ull) {
       if (lane == 0u) atomicCAS(status, 0, CRDT_ENONCANON);
       continue;
     }
-    // ---- out[i]'s arrays; self[i]'s used slots copied in (out caps >= self's: api.hip)
+    // ---- out[i]'s arrays; self[i]'s used slots copied in (out caps >= self's: api.hip's out_caps_ok)
     uint64_t* const keys = R.keys + i * Rk;
     uint64_t* const ecl = R.eclock + i * Rk * A;
     uint64_t* const vcl = R.vclock + i * Rk * A;
@@ -155,13 +106,14 @@ __global__ __launch_bounds__(kMoW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel
     uint64_t* const dcl = R.dclock + i * Rd * A;
     uint32_t* const dsn = R.dset_n + i * Rd;
     uint64_t* const dse = R.dset + i * Rd * Rs;
+    const DefRef def{dcl, dsn, dse, R.dcap, R.scap};  // the map's deferred removes (map_wave.h)
     copy_n(keys, S.keys + i * S.kcap, nS, lane);
     copy_n(ecl, S.eclock + i * S.kcap * A, nS * A, lane);
     copy_n(vcl, S.vclock + i * S.kcap * A, nS * A, lane);
     for (uint32_t k = 0; k < nS; ++k) {
       const uint64_t sk = i * S.kcap + k;
-      const uint32_t m = k < kMoW ? (uint32_t)__builtin_amdgcn_readlane(vmS, k) : uni(S.vn_mem[sk]);
-      const uint32_t dn = k < kMoW ? (uint32_t)__builtin_amdgcn_readlane(vdS, k) : uni(S.vn_def[sk]);
+      const uint32_t m = k < kW ? (uint32_t)__builtin_amdgcn_readlane(vmS, k) : uni32(S.vn_mem[sk]);
+      const uint32_t dn = k < kW ? (uint32_t)__builtin_amdgcn_readlane(vdS, k) : uni32(S.vn_def[sk]);
       if (lane == 0u) {
         vnm[k] = m;
         vnd[k] = dn;
@@ -171,7 +123,7 @@ __global__ __launch_bounds__(kMoW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel
       copy_n(vdc + k * Rv * A, S.vdclock + sk * S.vdcap * A, dn * A, lane);
       copy_n(vdn + k * Rv, S.vdset_n + sk * S.vdcap, dn, lane);
       const uint32_t vs = S.vscap;
-      for (uint32_t e = lane; e < dn * vs; e += kMoW) {  // the used part of each set
+      for (uint32_t e = lane; e < dn * vs; e += kW) {  // the used part of each set
         const uint32_t d = e / vs, o = e - d * vs;
         if (o < S.vdset_n[sk * S.vdcap + d]) vds[(k * Rv + d) * Rvs + o] = S.vdset[sk * S.vdcap * vs + e];
       }
@@ -180,7 +132,7 @@ __global__ __launch_bounds__(kMoW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel
     copy_n(dsn, S.dset_n + i * S.dcap, dS, lane);
     {
       const uint32_t ss = S.scap;
-      for (uint32_t e = lane; e < dS * ss; e += kMoW) {
+      for (uint32_t e = lane; e < dS * ss; e += kW) {
         const uint32_t d = e / ss, o = e - d * ss;
         if (o < S.dset_n[i * S.dcap + d]) dse[d * Rs + o] = S.dset[i * S.dcap * ss + e];
       }
@@ -196,9 +148,9 @@ __global__ __launch_bounds__(kMoW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel
     // keys[] is searched by every op: up to 64 keys are mirrored in LDS, so the
     // search costs no global round trip (an object that passes 64 keys goes on
     // searching out[i] itself)
-    bool kvalid = nS <= kMoW;
+    bool kvalid = nS <= kW;
     if (kvalid && lane < nS) lk[lane] = S.keys[i * S.kcap + lane];
-    mo_sync();
+    mw_sync();
     auto find_map_key = [&](uint64_t key, uint32_t& pos) -> bool {
       if (!kvalid) return find_key(keys, nk, key, lane, pos);
       const uint64_t x = lane < nk ? lk[lane] : ~0ull;
@@ -218,11 +170,11 @@ __global__ __launch_bounds__(kMoW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel
       copy_n(vmc + p * Rm * A, (const uint64_t*)W.row, W.nm * A, lane);
       copy_n(vdc + p * Rv * A, (const uint64_t*)W.dclk, W.nd * A, lane);
       copy_n(vdn + p * Rv, (const uint32_t*)W.dn, W.nd, lane);
-      for (uint32_t e = lane; e < W.nd * W.sw; e += kMoW) {  // only the used slots
+      for (uint32_t e = lane; e < W.nd * W.sw; e += kW) {  // only the used slots
         const uint32_t d = e / W.sw;
         if (e - d * W.sw < W.dn[d]) vds[p * Rv * Rvs + e] = W.dset[e];
       }
-      mo_sync();
+      mw_sync();
     };
     auto flush = [&]() {
       if (cur != kNone && dirty) store_entry();
@@ -243,7 +195,7 @@ __global__ __launch_bounds__(kMoW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel
       copy_n(W.dn, (const uint32_t*)(vdn + p * Rv), W.nd, lane);
       // capacity-strided (the workspace's stride is out's): no wait for the sizes
       copy_n(W.dset, (const uint64_t*)(vds + p * Rv * Rvs), W.nd * W.sw, lane);
-      mo_sync();
+      mw_sync();
     };
     // key slot src of out[i] to slot dst (its used part); the slot is not the staged one
     auto move_slot = [&](uint32_t dst_, uint32_t src_) {
@@ -255,7 +207,7 @@ __global__ __launch_bounds__(kMoW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel
       copy_n(vmc + dst * Rm * A, (const uint64_t*)(vmc + src * Rm * A), m * A, lane);
       copy_n(vdc + dst * Rv * A, (const uint64_t*)(vdc + src * Rv * A), dn * A, lane);
       copy_n(vdn + dst * Rv, (const uint32_t*)(vdn + src * Rv), dn, lane);
-      for (uint32_t e = lane; e < dn * W.sw; e += kMoW) {
+      for (uint32_t e = lane; e < dn * W.sw; e += kW) {
         const uint32_t d = e / W.sw;
         if (e - d * W.sw < vdn[src * Rv + d]) vds[dst * Rv * Rvs + e] = vds[src * Rv * Rvs + e];
       }
@@ -263,7 +215,7 @@ __global__ __launch_bounds__(kMoW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel
         vnm[dst] = m;
         vnd[dst] = dn;
       }
-      mo_sync();  // the next slot's copy overwrites what other lanes read here
+      mw_sync();  // the next slot's copy overwrites what other lanes read here
     };
 
     // apply_rm's entry edit (src/map.rs:341-349): the key's entry clock loses
@@ -280,7 +232,7 @@ __global__ __launch_bounds__(kMoW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel
         shift_down(keys, pos, nk, lane);
         if (kvalid) shift_down(lk, pos, nk, lane);
         --nk;
-        mo_sync();
+        mw_sync();
         return;
       }
       acquire(pos);
@@ -303,7 +255,7 @@ __global__ __launch_bounds__(kMoW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel
         }
         if (eq) {
           uint64_t* const set = W.dset + at * W.sw;
-          const uint32_t sn = uni(W.dn[at]);
+          const uint32_t sn = uni32(W.dn[at]);
           uint32_t p;
           if (!find_key(set, sn, member, lane, p)) {
             if (sn >= W.sw) return false;
@@ -316,12 +268,12 @@ __global__ __launch_bounds__(kMoW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel
         } else {
           if (W.nd >= c.DW) return false;
           for (uint32_t d = W.nd; d-- > at;) {  // entries from `at` one slot up, last first
-            const uint32_t sn = uni(W.dn[d]);
+            const uint32_t sn = uni32(W.dn[d]);
             const Row<NS> r = ldrow<NS>(W.dclk + d * A, A, lane);
             copy_n(W.dset + (d + 1u) * W.sw, (const uint64_t*)(W.dset + d * W.sw), sn, lane);
             strow<NS>(W.dclk + (d + 1u) * A, r, A, lane);
             if (lane == 0u) W.dn[d + 1u] = sn;
-            mo_sync();
+            mw_sync();
           }
           strow<NS>(W.dclk + at * A, C, A, lane);
           if (lane == 0u) {
@@ -330,7 +282,7 @@ __global__ __launch_bounds__(kMoW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel
           }
           ++W.nd;
         }
-        mo_sync();
+        mw_sync();
       }
       uint32_t mp;
       if (find_key(W.key, W.nm, member, lane, mp)) {
@@ -345,7 +297,7 @@ __global__ __launch_bounds__(kMoW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel
           shift_down(W.key, mp, W.nm, lane);
           --W.nm;
         }
-        mo_sync();
+        mw_sync();
       }
       return true;
     };
@@ -375,127 +327,42 @@ __global__ __launch_bounds__(kMoW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel
         vc.v[s] = dc;
       }
       strow<NS>(W.row + mp * A, r, A, lane);
-      mo_sync();
+      mw_sync();
       if (W.nd) ws_apply_deferred<NS>(W, vc, mdead, ddead, c, lane);
       return true;
     };
 
     uint64_t pb = 0ull;  // the staged pairs' first index
     for (uint64_t j = lo; j < hi && !err; ++j) {
-      const uint32_t t = (uint32_t)(j - lo) & (kMoW - 1u);
-      if (t == 0u) {
-        const bool inb = lane < hi - j;
-        const uint32_t k_ = inb ? P.kind[j + lane] : 0u, a_ = inb ? P.actor[j + lane] : 0u;
-        const uint64_t y_ = inb ? P.key[j + lane] : 0ull, c_ = inb ? P.counter[j + lane] : 0ull;
-        const uint64_t v_ = inb ? P.member[j + lane] : 0ull, e_ = inb ? P.clk_end[j + lane] : 0ull;
-        pb = j ? uni64(P.clk_end[j - 1u]) : 0ull;
-        const bool pin = pb < (uint64_t)P.n_clk && lane < (uint64_t)P.n_clk - pb;
-        const uint32_t pa_ = pin ? P.clk_act[pb + lane] : 0u;
-        const uint64_t pc_ = pin ? P.clk_ctr[pb + lane] : 0ull;
-        mo_sync();  // the previous chunk's reads of the stage are done
-        hkind[lane] = k_;
-        hact[lane] = a_;
-        hkey[lane] = y_;
-        hctr[lane] = c_;
-        hmem[lane] = v_;
-        hend[lane] = e_;
-        pact[lane] = pa_;
-        pctr[lane] = pc_;
-        mo_sync();
-      }
-      const uint32_t kind = uni(hkind[t]);
-      const uint64_t clo = t ? uni64(hend[t - 1u]) : pb, chi = uni64(hend[t]);
-      const uint64_t key = uni64(hkey[t]);
-      // an op clock is strictly increasing actors below A: at most A pairs
-      if (kind > CRDT_MAP_OP_UP_RM || clo > chi || chi > (uint64_t)P.n_clk || chi - clo > A) {
+      const uint32_t t = (uint32_t)(j - lo) & (kW - 1u);
+      if (t == 0u) pb = mapops::refill(ops, P, P.member, j, hi, lane);
+      mapops::OpHdr h;
+      if (!mapops::read_hdr(ops, P, t, pb, CRDT_MAP_OP_UP_RM, A, h)) {
         err = CRDT_ENONCANON;
         break;
       }
-      if (kind == CRDT_MAP_OP_NOP) continue;
-      // ---- the op's clock as a dense row (and its canonicity)
-      const uint32_t np = (uint32_t)(chi - clo);
-      mo_sync();  // the previous op's reads of oc are done
-      oc[lane] = 0ull;
-      oc[lane + kMoW] = 0ull;
-      mo_sync();
-      bool cbad = false;
-      if (chi - pb <= kMoW) {  // its pairs are staged, from slot clo - pb (clo >= pb: checked op by op)
-        const uint32_t f = (uint32_t)(clo - pb);
-        if (lane < np) {
-          const uint32_t a = pact[f + lane];
-          const uint64_t cc = pctr[f + lane];
-          cbad = cc == 0ull || a >= A || (lane && pact[f + lane - 1u] >= a);
-          if (a < A) oc[a] = cc;
-        }
-      } else {
-        for (uint32_t p = lane; p < np; p += kMoW) {
-          const uint32_t a = P.clk_act[clo + p];
-          const uint64_t cc = P.clk_ctr[clo + p];
-          cbad = cbad || cc == 0ull || a >= A || (p && P.clk_act[clo + p - 1u] >= a);
-          if (a < A) oc[a] = cc;
-        }
-      }
-      if (__ballot(cbad) != 0ull) {
+      if (h.kind == CRDT_MAP_OP_NOP) continue;
+      const mapops::OpClock<NS> oc = mapops::read_clock<NS>(ops, P, h, pb, A, lane);
+      if (!oc.ok) {
         err = CRDT_ENONCANON;
         break;
       }
-      mo_sync();
-      const Row<NS> C = ldrow<NS>(oc, A, lane);
+      const Row<NS>& C = oc.C;
+      const uint32_t kind = h.kind;
+      const uint64_t key = h.key;
 
       if (kind == CRDT_MAP_OP_RM) {
         if (!vle(C, cM)) {  // deferred: into an equal clock's key set, or a new entry in CLOCK ORDER
-          uint32_t at = nd;
-          bool eq = false;
-          for (uint32_t d = 0; d < nd; ++d) {
-            const int o = vorder(C, ldrow<NS>(dcl + (uint64_t)d * A, A, lane), lane);
-            if (o > 0) continue;
-            at = d;
-            eq = o == 0;
-            break;
-          }
-          if (eq) {
-            uint64_t* const set = dse + at * Rs;
-            const uint32_t sn = cnt0(dsn + at, lane);
-            uint32_t p;
-            if (!find_key(set, sn, key, lane, p)) {
-              if (sn >= R.scap) {
-                err = CRDT_ECAPACITY;
-                break;
-              }
-              shift_up(set, p, sn, lane);
-              if (lane == 0u) {
-                set[p] = key;
-                dsn[at] = sn + 1u;
-              }
-            }
-          } else {
-            if (nd >= R.dcap) {
-              err = CRDT_ECAPACITY;
-              break;
-            }
-            for (uint32_t d = nd; d-- > at;) {  // entries from `at` one slot up, last first
-              const uint32_t sn = cnt0(dsn + d, lane);
-              strow<NS>(dcl + (uint64_t)(d + 1u) * A, ldrow<NS>(dcl + (uint64_t)d * A, A, lane), A, lane);
-              copy_n(dse + (d + 1u) * Rs, (const uint64_t*)(dse + d * Rs), sn, lane);
-              if (lane == 0u) dsn[d + 1u] = sn;
-            }
-            // lane 0 writes the new set's only element: offset 0 is lane 0's in copy_n
-            strow<NS>(dcl + (uint64_t)at * A, C, A, lane);
-            if (lane == 0u) {
-              dse[at * Rs] = key;
-              dsn[at] = 1u;
-            }
-            ++nd;
-          }
-          mo_sync();
+          err = def_insert<NS>(def, nd, key, C, A, lane);
+          if (err) break;
         }
         rm_entry(key, C);
         continue;
       }
 
       // ---- Op::Up
-      const uint32_t da = uni(hact[t]);
-      const uint64_t dc = uni64(hctr[t]);
+      const uint32_t da = uni32(ops.hact[t]);
+      const uint64_t dc = uni64(ops.hctr[t]);
       if (da >= A) {
         err = CRDT_ENONCANON;
         break;
@@ -518,13 +385,13 @@ __global__ __launch_bounds__(kMoW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel
         for (uint32_t k = nk; k-- > pos;) move_slot(k + 1u, k);  // slots from pos one up, last first
         shift_up(keys, pos, nk, lane);
         if (lane == 0u) keys[pos] = key;
-        kvalid = kvalid && nk < kMoW;
+        kvalid = kvalid && nk < kW;
         if (kvalid) {
           shift_up(lk, pos, nk, lane);
           if (lane == 0u) lk[pos] = key;
         }
         ++nk;
-        mo_sync();
+        mw_sync();
         cur = pos;  // an empty clock and an empty set, in the workspace only
         ec = zrow<NS>();
         vc = zrow<NS>();
@@ -536,7 +403,7 @@ __global__ __launch_bounds__(kMoW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel
         ec.v[s] = ec.v[s] > dc ? ec.v[s] : dc;
         cM.v[s] = dc;
       }
-      const uint64_t member = uni64(hmem[t]);
+      const uint64_t member = uni64(ops.hpay[t]);
       if (!(kind == CRDT_MAP_OP_UP ? nested_add(member, ds, dl, dc) : nested_rm(member, C))) {
         err = CRDT_ECAPACITY;
         break;
@@ -549,14 +416,10 @@ __global__ __launch_bounds__(kMoW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel
         const uint32_t sn = cnt0(dsn + d, lane);
         for (uint32_t s = 0; s < sn; ++s) rm_entry(uni64(dse[d * Rs + s]), D);
         if (vle(D, cM)) continue;
-        if (w != d) {
-          strow<NS>(dcl + (uint64_t)w * A, D, A, lane);
-          copy_n(dse + w * Rs, (const uint64_t*)(dse + d * Rs), sn, lane);
-          if (lane == 0u) dsn[w] = sn;
-        }
+        if (w != d) def_move<NS>(def, w, d, A, lane);
         ++w;
       }
-      if (w != nd) mo_sync();
+      if (w != nd) mw_sync();
       nd = w;
     }
     if (err) {
@@ -590,15 +453,14 @@ int launch_map_orswot_apply(const crdt_map_orswot_slab& S, const crdt_map_orswot
   const size_t lds = map_orswot_apply_lds_bytes(R, A);
   if (lds > kOaLdsMax) return CRDT_EINVAL;
   const void* fn = A > 64u ? (const void*)map_orswot_apply_kernel<2> : (const void*)map_orswot_apply_kernel<1>;
-  int dev = 0, cus = 256, occ = 0;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  int occ = 0;
   // one single-wave block per resident slot (the workspace and the register bound size it)
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, kMoW, lds) != hipSuccess || occ < 1) occ = 16;
-  const uint64_t cap = (uint64_t)cus * (uint32_t)occ;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, kW, lds) != hipSuccess || occ < 1) occ = 16;
+  const uint64_t cap = (uint64_t)cu_count() * (uint32_t)occ;
   const uint32_t blocks = (uint32_t)(n_obj < cap ? n_obj : cap);
   if (hipMemsetAsync(ctl, 0, 4 * sizeof(uint32_t), stream) != hipSuccess) return CRDT_EHIP;  // ctl[3]: tickets
   void* args[] = {(void*)&S, (void*)&P, (void*)&R, &n_obj, &A, &status, &ctl};
-  if (hipLaunchKernel(fn, dim3(blocks), dim3(kMoW), args, lds, stream) != hipSuccess) return CRDT_EHIP;
+  if (hipLaunchKernel(fn, dim3(blocks), dim3(kW), args, lds, stream) != hipSuccess) return CRDT_EHIP;
   return hipGetLastError() == hipSuccess ? CRDT_OK : CRDT_EHIP;
 }
 

@@ -9,23 +9,12 @@
 #include <cstdint>
 
 #include "map_rows.h"
+#include "map_wave.h"
 
 namespace crdts_hip {
 namespace mows {
 
-using namespace maprow;  // Row<NS> and the VClock ops on it (map_rows.h)
-
-constexpr uint32_t kMoW = 64;
-
-__device__ __forceinline__ void mo_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ uint64_t uni64(uint64_t v) {
-  return ((uint64_t)uni((uint32_t)(v >> 32)) << 32) | (uint64_t)uni((uint32_t)v);
-}
+using namespace maprow;  // Row<NS> and the VClock ops on it (map_rows.h); the wave toolkit (map_wave.h)
 
 // A nested Orswot under construction (LDS). The top clock is a register
 // (lane = actor) held by the caller.
@@ -50,7 +39,7 @@ __device__ void ws_apply_deferred(Ws& W, Row<NS> clk, uint32_t* mdead, uint32_t*
                                   uint32_t lane) {
   for (uint32_t d = 0; d < W.nd; ++d) {
     const Row<NS> D = ldrow<NS>(W.dclk + d * c.A, c.A, lane);
-    const uint32_t n = uni(W.dn[d]);
+    const uint32_t n = uni32(W.dn[d]);
     for (uint32_t j = 0; j < n; ++j) {
       const uint64_t m = uni64(W.dset[d * W.sw + j]);
       uint32_t lo = 0, hi = W.nm;  // binary search over the (sorted) members
@@ -59,51 +48,51 @@ __device__ void ws_apply_deferred(Ws& W, Row<NS> clk, uint32_t* mdead, uint32_t*
         if (uni64(W.key[mid]) < m) lo = mid + 1u;
         else hi = mid;
       }
-      if (lo >= W.nm || uni64(W.key[lo]) != m || uni(mdead[lo])) continue;
+      if (lo >= W.nm || uni64(W.key[lo]) != m || uni32(mdead[lo])) continue;
       const Row<NS> r = vsub(ldrow<NS>(W.row + lo * c.A, c.A, lane), D);
       strow(W.row + lo * c.A, r, c.A, lane);
       const bool gone = !vany(r);
-      mo_sync();
+      mw_sync();
       if (gone && lane == 0u) mdead[lo] = 1u;
-      mo_sync();
+      mw_sync();
     }
     const bool drop = vle(D, clk);
     if (lane == 0u) ddead[d] = drop ? 1u : 0u;
   }
-  mo_sync();
+  mw_sync();
   // compaction, in place (destination <= source)
   uint32_t k = 0;
   for (uint32_t j = 0; j < W.nm; ++j) {
-    if (uni(mdead[j])) continue;
+    if (uni32(mdead[j])) continue;
     if (k != j) {
       const uint64_t key = W.key[j];
       const Row<NS> r = ldrow<NS>(W.row + j * c.A, c.A, lane);
-      mo_sync();
+      mw_sync();
       if (lane == 0u) W.key[k] = key;
       strow(W.row + k * c.A, r, c.A, lane);
-      mo_sync();
+      mw_sync();
     }
     ++k;
   }
   W.nm = k;
   k = 0;
   for (uint32_t d = 0; d < W.nd; ++d) {
-    if (uni(ddead[d])) continue;
+    if (uni32(ddead[d])) continue;
     if (k != d) {
       const Row<NS> D = ldrow<NS>(W.dclk + d * c.A, c.A, lane);
-      const uint32_t n = uni(W.dn[d]);
-      mo_sync();
+      const uint32_t n = uni32(W.dn[d]);
+      mw_sync();
       strow(W.dclk + k * c.A, D, c.A, lane);
       if (lane == 0u) W.dn[k] = n;
-      for (uint32_t j = lane; j < n; j += kMoW) W.dset[k * W.sw + j] = W.dset[d * W.sw + j];  // (rows k < d)
-      mo_sync();
+      for (uint32_t j = lane; j < n; j += kW) W.dset[k * W.sw + j] = W.dset[d * W.sw + j];  // (rows k < d)
+      mw_sync();
     }
     ++k;
   }
   W.nd = k;
-  for (uint32_t j = lane; j < c.MW; j += kMoW) mdead[j] = 0u;
-  for (uint32_t j = lane; j < c.DW; j += kMoW) ddead[j] = 0u;
-  mo_sync();
+  for (uint32_t j = lane; j < c.MW; j += kW) mdead[j] = 0u;
+  for (uint32_t j = lane; j < c.DW; j += kW) ddead[j] = 0u;
+  mw_sync();
 }
 
 // Orswot::truncate (src/orswot.rs:159-172) of W (top clock `clk`) by `t`.
@@ -117,12 +106,12 @@ __device__ void ws_truncate(Ws& W, Row<NS>& clk, Row<NS> t, uint32_t* mdead, uin
     if (covered && lane == 0u) mdead[j] = 1u;
   }
   clk = vmax(clk, t);
-  mo_sync();
+  mw_sync();
   ws_apply_deferred(W, clk, mdead, ddead, c, lane);
   // forget t from the top clock and every member clock (an emptied member stays)
   clk = vsub(clk, t);
   for (uint32_t j = 0; j < W.nm; ++j) strow(W.row + j * c.A, vsub(ldrow<NS>(W.row + j * c.A, c.A, lane), t), c.A, lane);
-  mo_sync();
+  mw_sync();
 }
 
 }  // namespace mows

@@ -13,7 +13,7 @@
 // One wave per object; lane = actor slot (map_rows.h). Every kernel is one
 // fused pass: self's used slots are read once and only the survivors are
 // written, at out slot w <= source slot k.
-//  - Map<u64, MVReg>: map_truncate_to (map_mvreg_ws.h).
+//  - Map<u64, MVReg>: map_truncate_to (map_mvreg_ws.h, on map_wave.h's toolkit).
 //  - Map<u64, Orswot>: each surviving key's set is staged in the LDS workspace
 //    (map_orswot_ws.h), truncated there by ws_truncate and written to slot w.
 //  - the nested map, two launches (after map_map_apply.hip): (1) the outer
@@ -26,24 +26,21 @@
 
 #include "../../include/crdts_hip.h"
 #include "kernels.h"
+#include "map_limits.h"
 #include "map_mvreg_ws.h"
 #include "map_orswot_ws.h"
 #include "map_rows.h"
+#include "map_wave.h"
 #include "sched.h"
 
 namespace crdts_hip {
 namespace {
 
-using namespace maprow;
-using mapws::DefRef;
-using mapws::kW;
-using mapws::mw_sync;
-using mapws::uni32;
-using mapws::uni64;
+using namespace maprow;  // rows (map_rows.h) and the wave toolkit with DefRef (map_wave.h)
 
 constexpr uint64_t kSrcNone = ~0ull;  // an unused out key slot: no task
-// self's deferred capacity limits (the merges' per-side limits)
-constexpr uint32_t kDefMax = 64, kDefMaxOrswot = 256;
+// (self's deferred capacity is within its side limit, map_limits.h: the `ord` arrays)
+static_assert(kMapMapDcap <= kMapMvregDcap, "the nested map's outer and inner lists share the kernels' ord[]");
 
 // TASKS (the nested map's second launch): n tasks, task t truncates S row
 // src[t] (kSrcNone: none) into R row t by clock row t / slots.
@@ -53,7 +50,7 @@ __global__ __launch_bounds__(kW) void map_mvreg_truncate_kernel(crdt_map_mvreg_s
                                                                 crdt_map_mvreg_slab R, uint64_t n, uint32_t A,
                                                                 int* __restrict__ status, uint32_t* __restrict__ ctl,
                                                                 const uint64_t* __restrict__ src, uint32_t slots) {
-  __shared__ uint32_t ord[kDefMax];  // the deferred survivors' order (S.dcap <= 64: api.hip)
+  __shared__ uint32_t ord[kMapMvregDcap];  // the deferred survivors' order
   const uint32_t lane = threadIdx.x;
   // (sched.h; TASKS: most tasks are empty slots, a plain stride balances them)
   typename std::conditional<TASKS, GridStride, BlockTickets<4>>::type sched(n, ctl + 3, lane);
@@ -74,7 +71,7 @@ __global__ __launch_bounds__(kW) void map_map_truncate_outer_kernel(crdt_map_map
                                                                     uint64_t n_obj, uint32_t A,
                                                                     int* __restrict__ status,
                                                                     uint32_t* __restrict__ ctl) {
-  __shared__ uint32_t ord[kDefMax];  // the deferred survivors' order (S.dcap <= 64: api.hip)
+  __shared__ uint32_t ord[kMapMvregDcap];  // the deferred survivors' order
   const uint32_t lane = threadIdx.x;
   const uint64_t Rk = R.kcap;
   BlockTickets<4> sched(n_obj, ctl + 3, lane);
@@ -108,12 +105,7 @@ __global__ __launch_bounds__(kW) void map_map_truncate_outer_kernel(crdt_map_map
         }
         ++w;
       }
-      DefRef def;
-      def.dcl = R.dclock + i * R.dcap * A;
-      def.dsn = R.dset_n + i * R.dcap;
-      def.dse = R.dset + i * R.dcap * R.scap;
-      def.Rd = R.dcap;
-      def.Rs = R.scap;
+      const DefRef def = def_ref(R, i, A);
       const uint32_t wd = mapws::def_truncate_to<NS>(S.dclock + i * S.dcap * A, S.dset_n + i * S.dcap,
                                                      S.dset + i * S.dcap * S.scap, S.scap, dS, def, T, ord, A, lane);
       strow<NS>(R.clock + i * A, vsub(rowv<NS>(S.clock, i, A, lane), T), A, lane);
@@ -130,13 +122,13 @@ __global__ __launch_bounds__(kW) void map_map_truncate_outer_kernel(crdt_map_map
 
 // Map<u64, Orswot>: the workspace is one nested set of self's capacities.
 template <int NS>
-__global__ __launch_bounds__(mows::kMoW) void map_orswot_truncate_kernel(crdt_map_orswot_slab S,
+__global__ __launch_bounds__(kW) void map_orswot_truncate_kernel(crdt_map_orswot_slab S,
                                                                          const uint64_t* __restrict__ clk,
                                                                          crdt_map_orswot_slab R, uint64_t n_obj,
                                                                          uint32_t A, int* __restrict__ status,
                                                                          uint32_t* __restrict__ ctl) {
   extern __shared__ uint64_t mt_lds[];
-  __shared__ uint32_t ord[kDefMaxOrswot];  // the map deferred survivors' order (S.dcap <= 256: api.hip)
+  __shared__ uint32_t ord[kMapOrswotDcap];  // the map deferred survivors' order
   const uint32_t lane = threadIdx.x;
   const uint64_t Sk = S.kcap, Sm = S.mcap, Sv = S.vdcap, Svs = S.vscap;
   const uint64_t Rk = R.kcap, Rm = R.mcap, Rv = R.vdcap, Rvs = R.vscap;
@@ -152,7 +144,7 @@ __global__ __launch_bounds__(mows::kMoW) void map_orswot_truncate_kernel(crdt_ma
   uint32_t* const ddead = W.dn + Sv;
   uint32_t* const mdead = ddead + Sv;
   for (uint32_t j = lane; j < S.vdcap + S.mcap; j += kW) ddead[j] = 0u;
-  mows::mo_sync();
+  mw_sync();
   BlockTickets<4> sched(n_obj, ctl + 3, lane);
   for (uint64_t i = sched.first(); i < n_obj; i = sched.next(i)) {
     // ---- the input row, checked as the merge checks it (map_orswot.hip)
@@ -194,7 +186,7 @@ __global__ __launch_bounds__(mows::kMoW) void map_orswot_truncate_kernel(crdt_ma
         const uint32_t d = e / W.sw;
         if (e - d * W.sw < S.vdset_n[sk * Sv + d]) W.dset[e] = S.vdset[sk * Sv * Svs + e];
       }
-      mows::mo_sync();
+      mw_sync();
       mows::ws_truncate<NS>(W, vc, T, mdead, ddead, c, lane);
       // ---- out key slot w
       strow<NS>(R.eclock + rw * A, ec, A, lane);
@@ -213,15 +205,10 @@ __global__ __launch_bounds__(mows::kMoW) void map_orswot_truncate_kernel(crdt_ma
         const uint32_t d = e / W.sw, o = e - d * W.sw;
         if (o < W.dn[d]) R.vdset[(rw * Rv + d) * Rvs + o] = W.dset[e];
       }
-      mows::mo_sync();  // the next key's stage overwrites what other lanes read here
+      mw_sync();  // the next key's stage overwrites what other lanes read here
       ++w;
     }
-    DefRef def;
-    def.dcl = R.dclock + i * R.dcap * A;
-    def.dsn = R.dset_n + i * R.dcap;
-    def.dse = R.dset + i * R.dcap * R.scap;
-    def.Rd = R.dcap;
-    def.Rs = R.scap;
+    const DefRef def = def_ref(R, i, A);
     const uint32_t wd = mapws::def_truncate_to<NS>(S.dclock + i * S.dcap * A, S.dset_n + i * S.dcap,
                                                    S.dset + i * S.dcap * S.scap, S.scap, dS, def, T, ord, A, lane);
     strow<NS>(R.clock + i * A, vsub(rowv<NS>(S.clock, i, A, lane), T), A, lane);
@@ -233,9 +220,7 @@ __global__ __launch_bounds__(mows::kMoW) void map_orswot_truncate_kernel(crdt_ma
 }
 
 uint32_t grid_cap() {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  return (uint32_t)cus * 28u;  // 7 single-wave blocks per SIMD, as the merges launch
+  return (uint32_t)cu_count() * 28u;  // 7 single-wave blocks per SIMD, as the merges launch
 }
 
 }  // namespace
@@ -275,15 +260,8 @@ int launch_map_map_truncate(const crdt_map_map_slab& S, const uint64_t* clk, con
     hipLaunchKernelGGL((map_map_truncate_outer_kernel<1>), dim3(blocks), dim3(kW), 0, stream, S, clk, R, src, n_obj, A,
                        status, ctl);
   if (hipGetLastError() != hipSuccess) return CRDT_EHIP;
-  // the kept keys are an object's first slots: a grid stride coprime with the
-  // slots per object spreads them over every block (map.hip)
   const uint64_t nt = n_obj * R.kcap;
-  blocks = (uint32_t)(nt < cap ? nt : cap);
-  auto gcd = [](uint32_t a, uint32_t b) {
-    while (b) { const uint32_t t = a % b; a = b; b = t; }
-    return a;
-  };
-  while (blocks > 1u && R.kcap > 1u && gcd(blocks, R.kcap) != 1u) --blocks;
+  blocks = coprime_grid((uint32_t)(nt < cap ? nt : cap), R.kcap);  // (sched.h)
   if (A > 64u)
     hipLaunchKernelGGL((map_mvreg_truncate_kernel<2, true>), dim3(blocks), dim3(kW), 0, stream, S.inner, clk, R.inner,
                        nt, A, status, ctl, src, R.kcap);
@@ -299,11 +277,10 @@ int launch_map_orswot_truncate(const crdt_map_orswot_slab& S, const uint64_t* cl
   const size_t lds = map_orswot_apply_lds_bytes(S, A);  // one nested set of self's capacities
   if (lds > kMapOrswotApplyLdsMax) return CRDT_EINVAL;
   const void* fn = A > 64u ? (const void*)map_orswot_truncate_kernel<2> : (const void*)map_orswot_truncate_kernel<1>;
-  int dev = 0, cus = 256, occ = 0;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  int occ = 0;
   // one single-wave block per resident slot (the workspace sizes it)
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, kW, lds) != hipSuccess || occ < 1) occ = 16;
-  const uint64_t cap = (uint64_t)cus * (uint32_t)occ;
+  const uint64_t cap = (uint64_t)cu_count() * (uint32_t)occ;
   const uint32_t blocks = (uint32_t)(n_obj < cap ? n_obj : cap);
   if (hipMemsetAsync(ctl, 0, 4 * sizeof(uint32_t), stream) != hipSuccess) return CRDT_EHIP;  // ctl[3]: tickets
   void* args[] = {(void*)&S, (void*)&clk, (void*)&R, &n_obj, &A, &status, &ctl};

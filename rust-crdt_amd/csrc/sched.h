@@ -15,6 +15,27 @@
 
 namespace crdts_hip {
 
+// The current device's CU count, asked at every launch (256 when the query
+// fails): the launchers size their resident grids by it.
+inline int cu_count() {
+  int dev = 0, cus = 256;
+  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  return cus;
+}
+
+// The largest grid <= blocks that shares no factor with `slots`: the kept keys
+// are an object's first slots, so a grid stride coprime with the slots per
+// object spreads them over every block (one sharing a factor with it would
+// leave the blocks of the last slots idle).
+inline uint32_t coprime_grid(uint32_t blocks, uint32_t slots) {
+  auto gcd = [](uint32_t a, uint32_t b) {
+    while (b) { const uint32_t t = a % b; a = b; b = t; }
+    return a;
+  };
+  while (blocks > 1u && slots > 1u && gcd(blocks, slots) != 1u) --blocks;
+  return blocks;
+}
+
 template <uint32_t K>
 struct BlockTickets {
   uint64_t n, unit, units, s_rounds, s_total, end = 0, k = 0;

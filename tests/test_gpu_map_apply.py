@@ -164,6 +164,66 @@ def test_map_apply_long_op_lists(gpu, oracle):
     _assert_rows(_apply(gpu, S, [ops for _, ops in batch], A, caps), E)
 
 
+# One op whose own clock has more than 64 pairs (possible only past 64 actors):
+# 100 pairs over actors 0..127 with gaps, actors 63, 64 and 127 among them. The
+# staged window holds 64 pairs, so the op's pairs are read from the op arrays,
+# 64 at a time, in two rounds.
+A128 = 128
+WIDE_CLOCK = [(a, a + 1) for a in range(A128) if a % 9 not in (2, 6)]
+
+
+def _wide_clock_batch():
+    """Three objects at 128 actors, each with entries under dots of actors 63,
+    64 and 127: the wide Rm as the first op of its list; as op 65 (the first of
+    the second staged chunk: its pairs start the refilled window); a wide Up
+    (its Put's clock) as op 4, inside a chunk whose window starts before it."""
+    pre = [("up", 63, 5, 7, [(63, 5)], 1), ("up", 64, 3, 7, [(63, 5), (64, 3)], 2),
+           ("up", 127, 200, 8, [(127, 200)], 3)]
+    fill = [("up", 1, n + 1, 9 + n % 3, [(1, n + 1)], 100 + n) for n in range(64)]
+    rm = ("rm", 7, WIDE_CLOCK)          # empties key 7's entry and is deferred (actor 127 is ahead of it)
+    up = ("up", 5, 9, 8, WIDE_CLOCK, 4)  # key 8's value (127, 200) is not covered: two values
+    return [(pre, [rm] + fill[:3]), (pre, fill + [rm, ("rm", 8, [(127, 200)])]), (pre, fill[:3] + [up, rm])]
+
+
+def test_map_apply_op_clock_past_64_pairs(gpu, oracle):
+    import crdts_hip
+
+    assert len(WIDE_CLOCK) == 100 and {63, 64, 127} <= {a for a, _ in WIDE_CLOCK}
+    batch = _wide_clock_batch()
+    lists = [ops for _, ops in batch]
+    assert lists[0][0][2] is WIDE_CLOCK and lists[1][64][2] is WIDE_CLOCK and lists[2][3][4] is WIDE_CLOCK
+    ops = crdts_hip.MapOps.from_lists(lists)
+    ends = np.asarray(crdts_hip.MapOps.arrays_from_lists(lists)[6]).astype(np.int64)
+    assert (np.diff(np.concatenate([[0], ends])) > 64).sum() == 4  # the batch holds ops with more than 64 pairs
+    caps = (8, 8, 8, 8)
+    S, E = map_opgen.oracle_slabs(oracle, batch, A128, caps, caps)
+    assert (E.a["n_def"] == 1).all() and (np.count_nonzero(E.a["dclock"][:, 0], axis=1) == 100).all()
+    assert E.a["mv_n"][2].max() == 2
+    _assert_rows(_apply(gpu, S, ops, A128, caps), E)
+
+
+@pytest.mark.parametrize("at", [0, 64])
+def test_map_apply_op_clock_past_64_pairs_noncanonical(gpu, at):
+    """The same clock with pair 70's actor repeated (in the second round of 64):
+    CRDT_ENONCANON for its object, the neighbour exact."""
+    import crdts_hip
+
+    bad = list(WIDE_CLOCK)
+    bad[70] = (bad[69][0], bad[70][1])
+    fill = [("up", 1, n + 1, 9, [(1, n + 1)], n) for n in range(at)]
+    S = crdts_hip.MapSlab.alloc(2, A128, *IN_CAPS)
+    exp = crdts_ref.Map(crdts_ref.MVReg)
+    map_opgen.apply_op(exp, GOOD[0])
+    E = crdts_hip.MapSlab.alloc(2, A128, *OUT_CAPS)
+    map_slab.mvreg_map_to_row(exp, E, 0, A128)
+    got = _apply(gpu, S, _raw_ops([GOOD, fill + [("rm", 3, bad)]]), A128, OUT_CAPS, check_status=False)
+    with pytest.raises(crdts_hip.CrdtError) as e:
+        gpu.status()
+    assert e.value.code == crdts_hip.CRDT_ENONCANON
+    _assert_rows(got, E, rows=[0])
+    gpu.status()
+
+
 # ------------------------------------------------- 3. actor-width boundaries
 @pytest.mark.parametrize("n_actors", [64, 65, 100, 128])
 def test_map_apply_actor_widths(gpu, oracle, n_actors):

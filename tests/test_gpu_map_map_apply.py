@@ -174,6 +174,68 @@ def _rm(key, clock):
     return {"rm": {"clock": [list(p) for p in clock], "key": key}}
 
 
+# One op whose own clock has more than 64 pairs (possible only past 64 actors):
+# 100 pairs over actors 0..127 with gaps, actors 63, 64 and 127 among them. The
+# staged window holds 64 pairs, so the op's pairs are read from the op arrays,
+# 64 at a time, in two rounds.
+A128 = 128
+WIDE_CLOCK = [(a, a + 1) for a in range(A128) if a % 9 not in (2, 6)]
+
+
+def _wide_clock_batch():
+    """Three objects at 128 actors, each with entries under dots of actors 63,
+    64 and 127: the wide Rm as the first op of its list; as op 65 (the first of
+    the second staged chunk: its pairs start the refilled window); wide Ups (a
+    Put's clock, an inner Rm's clock) as ops 4 and 5, inside a chunk whose
+    window starts before them."""
+    start = ng.replay(mkr.nested_map(), [_put((63, 5), 7, 1, [(63, 5)], 1), _put((64, 3), 7, 2, [(63, 5), (64, 3)], 2),
+                                         _put((127, 200), 8, 1, [(127, 200)], 3)])
+    fill = [_put((1, n + 1), 9 + n % 3, 1, [(1, n + 1)], 100 + n) for n in range(64)]
+    rm = _rm(7, WIDE_CLOCK)                    # empties key 7's entry and is deferred (actor 127 is ahead of it)
+    up = _put((5, 9), 8, 1, WIDE_CLOCK, 4)     # inner key 1's value (127, 200) is not covered: two values
+    irm = _irm((5, 10), 8, 1, WIDE_CLOCK)      # deferred in the inner map; only the value under (127, 200) stays
+    return [(start, [rm] + fill[:3]), (start, fill + [rm, _rm(8, [(127, 200)])]), (start, fill[:3] + [up, irm, rm])]
+
+
+def test_map_map_apply_op_clock_past_64_pairs(gpu):
+    import crdts_hip
+
+    assert len(WIDE_CLOCK) == 100 and {63, 64, 127} <= {a for a, _ in WIDE_CLOCK}
+    batch = _wide_clock_batch()
+    lists = [ops for _, ops in batch]
+    wide = [list(p) for p in WIDE_CLOCK]
+    assert lists[0][0]["rm"]["clock"] == wide and lists[1][64]["rm"]["clock"] == wide
+    assert lists[2][3]["up"]["op"]["up"]["op"]["put"]["clock"] == wide and lists[2][4]["up"]["op"]["rm"]["clock"] == wide
+    arrs = dict(zip(ng.OPS_FIELDS, crdts_hip.MapMapOps.arrays_from_lists(lists)))
+    ends = np.asarray(arrs["clk_end"]).astype(np.int64)
+    assert (np.diff(np.concatenate([[0], ends])) > 64).sum() == 5  # the batch holds ops with more than 64 pairs
+    caps, inner = (8, 8, 8), (8, 8, 8, 8)
+    S = ng.pack([s for s, _ in batch], A128, caps, inner)
+    E = ng.pack([ng.replay(s, ops) for s, ops in batch], A128, caps, inner)
+    assert (E.a["n_def"] == 1).all() and (np.count_nonzero(E.a["dclock"][:, 0], axis=1) == 100).all()
+    assert (np.count_nonzero(E.inner.a["dclock"].reshape(3, -1), axis=1) == [0, 0, 100]).all()  # the inner deferred Rm
+    ng.assert_rows(_apply(gpu, S, lists, A128, caps, inner), E)
+
+
+@pytest.mark.parametrize("at", [0, 64])
+def test_map_map_apply_op_clock_past_64_pairs_noncanonical(gpu, at):
+    """The same clock with pair 70's actor repeated (in the second round of 64):
+    CRDT_ENONCANON for its object, the neighbour exact."""
+    import crdts_hip
+
+    bad = list(WIDE_CLOCK)
+    bad[70] = (bad[69][0], bad[70][1])
+    fill = [_put((1, n + 1), 9, 1, [(1, n + 1)], n) for n in range(at)]
+    S = crdts_hip.MapMapSlab.alloc(2, A128, *IN_CAPS, IN_INNER)
+    E = ng.pack([ng.replay(mkr.nested_map(), GOOD), mkr.nested_map()], A128, ng.OUT_CAPS, ng.OUT_INNER)
+    got = _apply(gpu, S, _raw_ops([GOOD, fill + [_rm(3, bad)]]), A128, check_status=False)
+    with pytest.raises(crdts_hip.CrdtError) as e:
+        gpu.status()
+    assert e.value.code == crdts_hip.CRDT_ENONCANON
+    ng.assert_rows(got, E, rows=[0])
+    gpu.status()
+
+
 BIG = 100  # the outer key whose inner map is the large one
 
 
