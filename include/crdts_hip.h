@@ -1183,6 +1183,120 @@ int crdt_orswot_apply(crdt_ctx* ctx, const crdt_orswot_batch* self, const crdt_o
                       size_t out_bytes, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * Batched read path (read.hip): the reference's third verb, read -> ctx -> op.
+ *   Orswot::contains (src/orswot.rs:214-224), Orswot::value (:227-233),
+ *   Map::get (src/map.rs:291-302), Map::len (:282-288), and the contexts a
+ *   ReadCtx derives (src/ctx.rs:45-60): derive_rm_ctx().clock = rm_clock,
+ *   derive_add_ctx(actor) = { clock: add_clock with the dot witnessed, dot:
+ *   (actor, add_clock.get(actor) + 1) }.
+ * Queries are grouped per object like every op batch; a read changes nothing,
+ * so every query of a batch sees the same object. Per query:
+ *                 KEY (contains / get)             ALL (value / len)
+ *   val           1 present, 0 absent              members / entries
+ *   slot          the key's index, else NO_SLOT    NO_SLOT
+ *   add_clock     the top / map clock              the top / map clock
+ *   rm_clock      the member's / entry's clock     the top / map clock
+ *                 (empty if absent)
+ *   list          -                                the members / keys, ascending
+ *                                                  (value() is a HashSet in the
+ *                                                  reference; this is the
+ *                                                  record's own order)
+ * Two calls, like the egest codec: *_sizes writes the lengths (any array of
+ * crdt_read_sizes may be null = not wanted, and what is not wanted is not
+ * read: without add_len and dot_ctr the top clock is never touched; with an
+ * actor and dot_ctr only, a dense clock costs that actor's word); the caller
+ * takes the inclusive prefix sums of the lengths it wants; the write call puts
+ * query j's pairs at [end[j-1], end[j]) of the group's arrays. A group whose
+ * *_end is null is skipped. The pair arrays are in the op-clock form of
+ * crdt_orswot_ops, crdt_mvreg_ops and crdt_map_*_ops (clk_end / clk_act /
+ * clk_ctr: actors strictly increasing, counters > 0): rm_* of a batch of
+ * contains queries are the clocks of the Op::Rm's of the same members in the
+ * same order, add_* the Put clocks of Op::Up's, dot_ctr the dots' counters.
+ *
+ * crdt_orswot_read*: record batches with dense top clocks (flags 0) or
+ * CRDT_ORSWOT_SPARSE_CLOCK ones; a batch with gaps is valid input, and so is
+ * a record carrying CRDT_ORSWOT_EMPTY_MEMBER_CLOCK (contains of such a member:
+ * val 1, an empty rm clock — entries.get returns Some(empty)). No per-object
+ * limit beyond the record format's. add_len of a dense top clock is the count
+ * of its non-zero slots, of a sparse one n_clk, plus one for a new actor.
+ * crdt_map_read*: the four outer arrays the three Map slabs share (the view);
+ * get: add_clock = the map clock, rm_clock = the entry clock; len: both are
+ * the map clock. n_actors <= 128; kcap <= 8192, the largest slab an engine
+ * call can produce. `slot` makes the nested read get(k1).val.get(k2) a second
+ * call on `inner` with object i * kcap + slot.
+ * crdt_map_mvreg_get: the val: Option<MVReg> of Map::get for Map<u64, MVReg>:
+ * query j's register is copied into row j of a slab in crdt_mvreg_merge's
+ * layout (d_out_n[n_q], d_out_clk[n_q][out_cap][n_actors], d_out_val[n_q]
+ * [out_cap]; Vec order, unused slots zero-filled), ready for crdt_mvreg_merge,
+ * crdt_mvreg_apply and crdt_mvreg_read_clock. An absent key and an ALL query
+ * give n = 0. Only kind and key of the queries are read.
+ * Out of scope: the value of get for Map<u64, Orswot> and the nested map (a
+ * slab-to-record conversion); their ctx (val, slot, clocks) is served by the
+ * common view.
+ *
+ * CRDT_EINVAL (before any device work): a null ctx or struct; with n_obj > 0 a
+ * null batch / view array or obj_end; with n_q > 0 a null kind or key, (write
+ * call) a wanted group's null array, (crdt_map_mvreg_get) a null output or
+ * nested array; n_actors == 0 (maps: or > 128); kcap == 0 or > 8192; flags
+ * other than 0 or CRDT_ORSWOT_SPARSE_CLOCK; an output array equal to an input
+ * array; out_cap < slab.mcap. Otherwise n_obj == 0 is CRDT_OK.
+ * Latched (crdt_ctx_status), the other queries and objects unaffected:
+ *   CRDT_ENONCANON  an obj_end that decreases or runs past n_q (the object's
+ *                   queries are not written, as in crdt_vclock_dense_get); a
+ *                   record whose header counts do not fit its extent, whose
+ *                   extent leaves [0, bytes) or whose clock form is not the
+ *                   batch's, a map row with n_keys > kcap, an unknown kind
+ *                   among the object's queries (every size of the object's
+ *                   queries is 0, slot NO_SLOT); an actor >= n_actors other than
+ *                   NO_ACTOR, and an actor whose counter is 2^64 - 1, where
+ *                   the reference's inc overflows (src/vclock.rs:182-185):
+ *                   dot_ctr 0, the query answered as without an actor;
+ *                   crdt_map_mvreg_get: a register count above mcap (n = 0).
+ *   CRDT_ECAPACITY  (write call) a span end[j] - end[j-1] that is not the
+ *                   query's length or leaves [0, n): the query's group is not
+ *                   written; nothing outside the arrays is touched.
+ * Sortedness is taken as given (as crdt_vclock_csr_get): no deep validation.
+ * ------------------------------------------------------------------------ */
+#define CRDT_READ_KEY 0u            /* Orswot::contains(member) / Map::get(key)            */
+#define CRDT_READ_ALL 1u            /* Orswot::value()          / Map::len()               */
+#define CRDT_READ_NO_ACTOR 0xFFFFFFFFu
+#define CRDT_READ_NO_SLOT  0xFFFFFFFFu
+typedef struct crdt_read_queries {  /* device arrays */
+  const uint64_t* obj_end;  /* n_obj: object i's queries are [obj_end[i-1], obj_end[i]) */
+  const uint32_t* kind;     /* n_q */
+  const uint64_t* key;      /* n_q: member / map key (KEY queries)                      */
+  const uint32_t* actor;    /* n_q, or null: the actor to derive an AddCtx for          */
+  size_t n_q;
+} crdt_read_queries;
+typedef struct crdt_read_sizes {    /* device, n_q each, written by the *_sizes call; any may be null = not wanted */
+  uint64_t* val;       /* KEY: 1 present / 0 absent.  ALL: number of members / entries  */
+  uint32_t* slot;      /* KEY: index of the key among the object's members / entries, else NO_SLOT */
+  uint64_t* dot_ctr;   /* derive_add_ctx(actor).dot.counter = add_clock.get(actor) + 1; 0 without an actor */
+  uint32_t* add_len;   /* pairs of AddCtx.clock (add_clock with that dot witnessed); of add_clock itself without an actor */
+  uint32_t* rm_len;    /* pairs of rm_clock: KEY: the member's / entry's clock (0 if absent); ALL: the top / map clock */
+  uint32_t* list_len;  /* ALL: members / keys listed (= val); KEY: 0                    */
+} crdt_read_sizes;
+typedef struct crdt_read_out {      /* device; a group whose *_end is null is skipped */
+  const uint64_t* add_end; uint32_t* add_act; uint64_t* add_ctr; size_t n_add;
+  const uint64_t* rm_end;  uint32_t* rm_act;  uint64_t* rm_ctr;  size_t n_rm;
+  const uint64_t* list_end; uint64_t* list_key; size_t n_list;   /* ascending */
+} crdt_read_out;
+typedef struct crdt_map_read_view {
+  const uint64_t* clock; const uint32_t* n_keys; const uint64_t* keys; const uint64_t* eclock; uint32_t kcap;
+} crdt_map_read_view;
+int crdt_orswot_read_sizes(crdt_ctx* ctx, const crdt_orswot_batch* batch, const crdt_read_queries* queries,
+                           uint32_t n_actors, uint32_t flags, const crdt_read_sizes* sizes, void* stream);
+int crdt_orswot_read(crdt_ctx* ctx, const crdt_orswot_batch* batch, const crdt_read_queries* queries,
+                     uint32_t n_actors, uint32_t flags, const crdt_read_out* out, void* stream);
+int crdt_map_read_sizes(crdt_ctx* ctx, const crdt_map_read_view* view, const crdt_read_queries* queries,
+                        size_t n_obj, uint32_t n_actors, const crdt_read_sizes* sizes, void* stream);
+int crdt_map_read(crdt_ctx* ctx, const crdt_map_read_view* view, const crdt_read_queries* queries, size_t n_obj,
+                  uint32_t n_actors, const crdt_read_out* out, void* stream);
+int crdt_map_mvreg_get(crdt_ctx* ctx, const crdt_map_mvreg_slab* slab, const crdt_read_queries* queries,
+                       size_t n_obj, uint32_t n_actors, uint32_t* d_out_n, uint64_t* d_out_clk,
+                       uint64_t* d_out_val, uint32_t out_cap, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * Ingest / egest: the reference's binary form <-> canonical records
  * (SURVEY.md §8(f) rank 1). The reference form of an Orswot<M, A> is
  * `to_binary(&s)` = bincode 0.9 of its serde derives (src/lib.rs:62-83;

@@ -26,6 +26,7 @@ __all__ = [
     "Orswot", "VClock", "GCounter", "PNCounter", "merge_batch", "decode_record", "encode_record",
     "record_bytes", "CONFIG3", "EXPORTS", "LIB_PATH", "CONFIG5", "SPARSE_CLOCK", "generate_replicas", "ClockBatch",
     "generate_clocks_csr", "MapMapSlab", "MapOps", "MapMapOps", "MVRegOps", "ClockOps",
+    "ReadQueries",
 ]
 
 # SURVEY.md §8(d) config 3 / BASELINE.json configs[2].
@@ -401,6 +402,77 @@ class ClockOps:
         return cls.from_arrays(*cls.arrays_from_lists(per_obj, with_dir), device=device)
 
 
+class ReadQueries:
+    """A batch of reads (crdt_read_queries), grouped per object:
+    Orswot::contains / Map::get (KEY) and Orswot::value / Map::len (ALL), each
+    with the actor to derive an AddCtx for, or NO_ACTOR. Tensors: obj_end int64
+    [n_obj], kind int32 [n_q], key int64 [n_q] (u64 bits), actor int32 [n_q] or
+    None (no query names an actor)."""
+
+    KEY, ALL = 0, 1
+    NO_ACTOR = 0xFFFFFFFF
+    NO_SLOT = 0xFFFFFFFF
+
+    def __init__(self, obj_end, kind, key, actor=None):
+        self.t = (obj_end, kind, key, actor)
+        self.n_obj = int(obj_end.numel())
+        self.n_q = int(kind.numel())
+
+    def cqueries(self):
+        from ._lib import ReadQueriesC
+
+        p = [C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None for t in self.t]
+        return ReadQueriesC(*p, self.n_q)
+
+    @classmethod
+    def from_arrays(cls, obj_end, kind, key, actor=None, device=0):
+        """Host numpy arrays (u64 / u32 as in crdt_read_queries) -> device; not
+        validated. device None: the tensors stay on the host."""
+        torch = _torch()
+
+        def put(x, dt):
+            if x is None:
+                return None
+            x = np.ascontiguousarray(np.asarray(x, dtype=dt))
+            t = torch.from_numpy(x.view(np.int32 if dt == np.uint32 else np.int64))
+            return t if device is None else t.to(f"cuda:{device}")
+
+        return cls(put(obj_end, np.uint64), put(kind, np.uint32), put(key, np.uint64), put(actor, np.uint32))
+
+    @staticmethod
+    def arrays_from_lists(per_obj):
+        """per_obj[i] = [("key", k) | ("key", k, actor) | ("all",) | ("all", actor), ...]
+        -> (obj_end u64 [n_obj], kind u32 [n_q], key u64 [n_q], actor u32 [n_q]
+        or None when no query names an actor). An actor of None is NO_ACTOR."""
+        ends, kind, key, act = [], [], [], []
+        for qs in per_obj:
+            for q in qs:
+                if q[0] == "key":
+                    kind.append(ReadQueries.KEY); key.append(q[1]); a = q[2] if len(q) > 2 else None
+                else:
+                    kind.append(ReadQueries.ALL); key.append(0); a = q[1] if len(q) > 1 else None
+                act.append(ReadQueries.NO_ACTOR if a is None else a)
+            ends.append(len(kind))
+        named = any(a != ReadQueries.NO_ACTOR for a in act)
+        return (np.asarray(ends, np.uint64), np.asarray(kind, np.uint32), np.asarray(key, np.uint64),
+                np.asarray(act, np.uint32) if named else None)
+
+    @classmethod
+    def from_lists(cls, per_obj, device=0):
+        """per_obj[i] = object i's queries, see arrays_from_lists."""
+        return cls.from_arrays(*cls.arrays_from_lists(per_obj), device=device)
+
+
+READ_WANTS = ("val", "slot", "dot", "add", "rm", "list")
+
+
+def _read_view(a, kcap):
+    """crdt_map_read_view of a Map slab's arrays (device tensors)."""
+    from ._lib import MapReadViewC
+
+    return MapReadViewC(*[C.c_void_p(a[f].data_ptr()) for f in ("clock", "n_keys", "keys", "eclock")], kcap)
+
+
 class MapMapOps:
     """A batch of Map<u64, Map<u64, MVReg<u64, A>, A>, A> ops (the reference's
     TestMap: Op::Nop / Op::Rm / Op::Up whose inner op is again a Map op,
@@ -626,6 +698,9 @@ class MapSlab:
                (self.a[f] for f in self.FIELDS)]
         return MapSlabC(*ptr, self.kcap, self.mcap, self.dcap, self.scap)
 
+    def read_view(self):
+        return _read_view(self.a, self.kcap)
+
 
 class MapMapSlab:
     """Dense slab of Map<u64, Map<u64, MVReg<u64, A>, A>, A> states — the
@@ -717,6 +792,10 @@ class MapMapSlab:
                for f in MAP_MAP_FIELDS]
         return MapMapSlabC(*ptr, self.kcap, self.dcap, self.scap, self.inner.cstruct())
 
+    def read_view(self):
+        """The outer map's view; the nested maps are read through inner.read_view()."""
+        return _read_view(self.a, self.kcap)
+
 
 class MapOrswotSlab:
     """Dense fixed-capacity slab of Map<u64, Orswot<u64, A>, A> states
@@ -804,6 +883,9 @@ class MapOrswotSlab:
         ptr = [C.c_void_p(self.a[f].data_ptr() if hasattr(self.a[f], "data_ptr") else self.a[f].ctypes.data)
                for f in MAP_ORSWOT_FIELDS]
         return MapOrswotSlabC(*ptr, *[self.caps[k] for k in MAP_ORSWOT_CAPS])
+
+    def read_view(self):
+        return _read_view(self.a, self.caps["kcap"])
 
 
 class Engine:
@@ -1386,6 +1468,91 @@ class Engine:
         if check_status:
             self.status(stream)
         return OrswotBatch(base, off, B.n_actors, int(base.numel()), B.flags)
+
+    # ------------------------------------------------ batched read path
+    def _read(self, sizes_call, write_call, queries: "ReadQueries", want, stream, check_status):
+        """The two-call protocol: sizes (zero-initialised), the inclusive prefix
+        sums of the wanted groups' lengths on the device, write. Returns a
+        dict of device tensors: val, slot, dot_ctr, and per wanted group g in
+        add / rm: g_len, g_end, g_act, g_ctr; list: list_len, list_end, list_key."""
+        from ._lib import READ_SIZES_FIELDS, ReadOutC, ReadSizesC
+
+        torch = _torch()
+        bad = set(want) - set(READ_WANTS)
+        if bad:
+            raise CrdtError(CRDT_EINVAL, f"read: unknown want {sorted(bad)}")
+        dev = queries.t[0].device
+        n_q = queries.n_q
+        name = {"val": "val", "slot": "slot", "dot": "dot_ctr", "add": "add_len", "rm": "rm_len", "list": "list_len"}
+        res = {name[w]: torch.zeros(n_q, dtype=torch.int64 if w in ("val", "dot") else torch.int32, device=dev)
+               for w in READ_WANTS if w in want}
+        q = queries.cqueries()
+        z = ReadSizesC(*[C.c_void_p(res[f].data_ptr()) if f in res and n_q else None for f in READ_SIZES_FIELDS])
+        st = self._stream(stream)
+        check(sizes_call(C.byref(q), C.byref(z), st), "read_sizes")
+        groups = [g for g in ("add", "rm", "list") if g in want]
+        if groups:
+            with torch.cuda.stream(stream) if stream is not None else _nullctx():
+                for g in groups:
+                    res[g + "_end"] = torch.cumsum(res[g + "_len"].to(torch.int64), 0)
+                totals = {g: int(res[g + "_end"][-1].item()) if n_q else 0 for g in groups}
+            o = ReadOutC()
+            for g in groups:
+                n = totals[g]
+                setattr(o, "n_" + g, n)
+                setattr(o, g + "_end", res[g + "_end"].data_ptr() if n_q else None)
+                if g == "list":
+                    res["list_key"] = torch.empty(n, dtype=torch.int64, device=dev)
+                    o.list_key = res["list_key"].data_ptr() if n else None
+                else:
+                    res[g + "_act"] = torch.empty(n, dtype=torch.int32, device=dev)
+                    res[g + "_ctr"] = torch.empty(n, dtype=torch.int64, device=dev)
+                    setattr(o, g + "_act", res[g + "_act"].data_ptr() if n else None)
+                    setattr(o, g + "_ctr", res[g + "_ctr"].data_ptr() if n else None)
+            check(write_call(C.byref(q), C.byref(o), st), "read")
+        if check_status:
+            self.status(stream)
+        return res
+
+    def orswot_read(self, B: "OrswotBatch", queries: "ReadQueries", want=("val", "rm"), stream=None,
+                    check_status=True):
+        """Orswot::contains / value (src/orswot.rs:214-233) and the contexts
+        derived from them (src/ctx.rs:45-60) for every query, on the device.
+        want: any of val, slot, dot, add, rm, list — what is not wanted is
+        not read. The rm / add groups are in the op-clock form of OrswotOps
+        (clk_end / clk_act / clk_ctr), dot_ctr is the Add's counter."""
+        b = B.cbatch()
+        return self._read(
+            lambda q, z, st: lib.crdt_orswot_read_sizes(self.ctx, C.byref(b), q, B.n_actors, B.flags, z, st),
+            lambda q, o, st: lib.crdt_orswot_read(self.ctx, C.byref(b), q, B.n_actors, B.flags, o, st),
+            queries, want, stream, check_status)
+
+    def map_read(self, S, queries: "ReadQueries", n_actors, want=("val", "slot", "rm"), stream=None,
+                 check_status=True):
+        """Map::get / len (src/map.rs:282-302) and their contexts over the outer
+        arrays of any of the three Map slabs (S.read_view()); `slot` is the
+        key's index among the entries, the handle of the nested value."""
+        v = S.read_view()
+        n = int(S.a["n_keys"].shape[0])
+        return self._read(
+            lambda q, z, st: lib.crdt_map_read_sizes(self.ctx, C.byref(v), q, n, n_actors, z, st),
+            lambda q, o, st: lib.crdt_map_read(self.ctx, C.byref(v), q, n, n_actors, o, st),
+            queries, want, stream, check_status)
+
+    def map_mvreg_get(self, S: "MapSlab", queries: "ReadQueries", n_actors, out_cap=None, out=None, stream=None,
+                      check_status=True):
+        """The value of Map::get (src/map.rs:291-302) for Map<u64, MVReg>: query
+        j's register as row j of an MVReg slab (n, clocks [n_q][cap][A], vals
+        [n_q][cap]), unused slots zero-filled; n = 0 for an absent key."""
+        cap = int(out[2].shape[1]) if out is not None else int(out_cap or S.mcap)
+        outn, outc, outv = self._mvreg_out(queries.n_q, cap, n_actors, S.a["clock"].device, out)
+        s, q = S.cstruct(), queries.cqueries()
+        p = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None  # noqa: E731
+        check(lib.crdt_map_mvreg_get(self.ctx, C.byref(s), C.byref(q), int(S.a["n_keys"].shape[0]), n_actors,
+                                     p(outn), p(outc), p(outv), cap, self._stream(stream)), "map_mvreg_get")
+        if check_status:
+            self.status(stream)
+        return outn, outc, outv
 
     # ------------------------------------------------ bincode ingest / egest
     def orswot_from_bincode(self, blobs, blob_off, blob_len, n_actors, actor_bytes, member_bytes, flags=0,

@@ -90,6 +90,7 @@ EXPORTS = [
     "crdt_vclock_dense_subtract", "crdt_vclock_dense_intersection", "crdt_gcounter_value", "crdt_pncounter_value",
     "crdt_vclock_dense_get", "crdt_vclock_csr_truncate", "crdt_vclock_csr_subtract", "crdt_vclock_csr_intersection",
     "crdt_vclock_csr_apply", "crdt_gcounter_csr_apply", "crdt_gcounter_csr_value", "crdt_vclock_csr_get",
+    "crdt_orswot_read_sizes", "crdt_orswot_read", "crdt_map_read_sizes", "crdt_map_read", "crdt_map_mvreg_get",
 ]
 
 CRDT_COMM_ID_BYTES = 128
@@ -179,6 +180,31 @@ class ClockCsr(C.Structure):
 class ClockOpsC(C.Structure):
     """crdt_clock_ops (include/crdts_hip.h)."""
     _fields_ = [(f, C.c_void_p) for f in ("obj_end", "actor", "counter", "dir")] + [("n_ops", C.c_size_t)]
+
+
+class ReadQueriesC(C.Structure):
+    """crdt_read_queries (include/crdts_hip.h)."""
+    _fields_ = [(f, C.c_void_p) for f in ("obj_end", "kind", "key", "actor")] + [("n_q", C.c_size_t)]
+
+
+READ_SIZES_FIELDS = ("val", "slot", "dot_ctr", "add_len", "rm_len", "list_len")
+
+
+class ReadSizesC(C.Structure):
+    """crdt_read_sizes (include/crdts_hip.h)."""
+    _fields_ = [(f, C.c_void_p) for f in READ_SIZES_FIELDS]
+
+
+class ReadOutC(C.Structure):
+    """crdt_read_out (include/crdts_hip.h)."""
+    _fields_ = [("add_end", C.c_void_p), ("add_act", C.c_void_p), ("add_ctr", C.c_void_p), ("n_add", C.c_size_t),
+                ("rm_end", C.c_void_p), ("rm_act", C.c_void_p), ("rm_ctr", C.c_void_p), ("n_rm", C.c_size_t),
+                ("list_end", C.c_void_p), ("list_key", C.c_void_p), ("n_list", C.c_size_t)]
+
+
+class MapReadViewC(C.Structure):
+    """crdt_map_read_view (include/crdts_hip.h)."""
+    _fields_ = [(f, C.c_void_p) for f in ("clock", "n_keys", "keys", "eclock")] + [("kcap", C.c_uint32)]
 
 
 class ClockCsrOut(C.Structure):
@@ -326,6 +352,12 @@ def _load():
         "crdt_gcounter_csr_apply": (I, [P, C.POINTER(ClockCsr), C.POINTER(ClockOpsC), C.POINTER(ClockCsrOut), P]),
         "crdt_gcounter_csr_value": (I, [P, C.POINTER(ClockCsr), P, P]),
         "crdt_vclock_csr_get": (I, [P, C.POINTER(ClockCsr), C.POINTER(ClockOpsC), P, P]),
+        "crdt_orswot_read_sizes": (I, [P, BP, C.POINTER(ReadQueriesC), U32, U32, C.POINTER(ReadSizesC), P]),
+        "crdt_orswot_read": (I, [P, BP, C.POINTER(ReadQueriesC), U32, U32, C.POINTER(ReadOutC), P]),
+        "crdt_map_read_sizes": (I, [P, C.POINTER(MapReadViewC), C.POINTER(ReadQueriesC), SZ, U32,
+                                    C.POINTER(ReadSizesC), P]),
+        "crdt_map_read": (I, [P, C.POINTER(MapReadViewC), C.POINTER(ReadQueriesC), SZ, U32, C.POINTER(ReadOutC), P]),
+        "crdt_map_mvreg_get": (I, [P, C.POINTER(MapSlabC), C.POINTER(ReadQueriesC), SZ, U32, P, P, P, U32, P]),
         "crdt_orswot_generate_replicas_subset": (I, [U64, SZ, SZ, C.POINTER(RepParams), U32, U32, U32, U32, I,
                                                      C.POINTER(P)]),
         "crdt_orswot_replica_join_transport": (I, [P, C.POINTER(TransportC), BP, U32, U32, P, P, SZ, C.POINTER(SZ),

@@ -1160,4 +1160,104 @@ int crdt_map_map_to_bincode(crdt_ctx* ctx, const crdt_map_map_slab* slab, size_t
                                       nullptr, d_out, d_out_off, out_bytes, ctx->d_status, S(stream));
 }
 
+// ---------------------------------------------------------------- the read path
+namespace {
+constexpr uint32_t kReadKcapMax = kMapOutFactor * kMapMvregKcap;  // the three slabs' output kcap limit
+static_assert(kMapOrswotKcap == kMapMvregKcap && kMapMapKcap == kMapMvregKcap, "one kcap limit for the view");
+
+bool read_queries_ok(const crdt_read_queries* q, size_t n_obj) {
+  return q && !(n_obj && !q->obj_end) && !(q->n_q && (!q->kind || !q->key));
+}
+// Is a (non-null) output array w one of the input arrays?
+bool read_alias(const void* w, const crdt_read_queries* q, std::initializer_list<const void*> state) {
+  if (!w) return false;
+  for (const void* r : {(const void*)q->obj_end, (const void*)q->kind, (const void*)q->key, (const void*)q->actor})
+    if (w == r) return true;
+  for (const void* r : state)
+    if (w == r) return true;
+  return false;
+}
+bool read_sizes_alias(const crdt_read_sizes* z, const crdt_read_queries* q, std::initializer_list<const void*> state) {
+  for (const void* w : {(const void*)z->val, (const void*)z->slot, (const void*)z->dot_ctr, (const void*)z->add_len,
+                        (const void*)z->rm_len, (const void*)z->list_len})
+    if (read_alias(w, q, state)) return true;
+  return false;
+}
+// The write call's groups: a wanted group has all its arrays (with queries to
+// write), and no output is an input (the *_end arrays are inputs too).
+bool read_out_ok(const crdt_read_out* o, const crdt_read_queries* q, std::initializer_list<const void*> state) {
+  if (q->n_q) {
+    if (o->add_end && o->n_add && (!o->add_act || !o->add_ctr)) return false;
+    if (o->rm_end && o->n_rm && (!o->rm_act || !o->rm_ctr)) return false;
+    if (o->list_end && o->n_list && !o->list_key) return false;
+  }
+  for (const void* w : {(const void*)o->add_act, (const void*)o->add_ctr, (const void*)o->rm_act,
+                        (const void*)o->rm_ctr, (const void*)o->list_key}) {
+    if (read_alias(w, q, state)) return false;
+    if (w && (w == o->add_end || w == o->rm_end || w == o->list_end)) return false;
+  }
+  return true;
+}
+int orswot_read(crdt_ctx* ctx, const crdt_orswot_batch* b, const crdt_read_queries* q, uint32_t n_actors,
+                uint32_t flags, const crdt_read_sizes* sizes, const crdt_read_out* out, bool write, void* stream) {
+  if (!ctx || !b || (write ? !out : !sizes) || n_actors == 0 || (flags & ~CRDT_ORSWOT_SPARSE_CLOCK) ||
+      !read_queries_ok(q, b->n_obj))
+    return CRDT_EINVAL;
+  if (b->n_obj && (!b->base || !b->off)) return CRDT_EINVAL;
+  const std::initializer_list<const void*> state = {b->base, b->off};
+  if (write ? !read_out_ok(out, q, state) : read_sizes_alias(sizes, q, state)) return CRDT_EINVAL;
+  if (b->n_obj == 0) return CRDT_OK;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_orswot_read(*b, *q, n_actors, flags, sizes, out, ctx->d_status, S(stream));
+}
+int map_read(crdt_ctx* ctx, const crdt_map_read_view* v, const crdt_read_queries* q, size_t n_obj, uint32_t n_actors,
+             const crdt_read_sizes* sizes, const crdt_read_out* out, bool write, void* stream) {
+  if (!ctx || !v || (write ? !out : !sizes) || !map_actors_ok(n_actors) || !cap_ok(v->kcap, kReadKcapMax) ||
+      !read_queries_ok(q, n_obj))
+    return CRDT_EINVAL;
+  if (n_obj && (!v->clock || !v->n_keys || !v->keys || !v->eclock)) return CRDT_EINVAL;
+  const std::initializer_list<const void*> state = {v->clock, v->n_keys, v->keys, v->eclock};
+  if (write ? !read_out_ok(out, q, state) : read_sizes_alias(sizes, q, state)) return CRDT_EINVAL;
+  if (n_obj == 0) return CRDT_OK;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_map_read(*v, *q, n_obj, n_actors, sizes, out, ctx->d_status, S(stream));
+}
+}  // namespace
+
+int crdt_orswot_read_sizes(crdt_ctx* ctx, const crdt_orswot_batch* batch, const crdt_read_queries* queries,
+                           uint32_t n_actors, uint32_t flags, const crdt_read_sizes* sizes, void* stream) {
+  return orswot_read(ctx, batch, queries, n_actors, flags, sizes, nullptr, false, stream);
+}
+int crdt_orswot_read(crdt_ctx* ctx, const crdt_orswot_batch* batch, const crdt_read_queries* queries,
+                     uint32_t n_actors, uint32_t flags, const crdt_read_out* out, void* stream) {
+  return orswot_read(ctx, batch, queries, n_actors, flags, nullptr, out, true, stream);
+}
+int crdt_map_read_sizes(crdt_ctx* ctx, const crdt_map_read_view* view, const crdt_read_queries* queries,
+                        size_t n_obj, uint32_t n_actors, const crdt_read_sizes* sizes, void* stream) {
+  return map_read(ctx, view, queries, n_obj, n_actors, sizes, nullptr, false, stream);
+}
+int crdt_map_read(crdt_ctx* ctx, const crdt_map_read_view* view, const crdt_read_queries* queries, size_t n_obj,
+                  uint32_t n_actors, const crdt_read_out* out, void* stream) {
+  return map_read(ctx, view, queries, n_obj, n_actors, nullptr, out, true, stream);
+}
+int crdt_map_mvreg_get(crdt_ctx* ctx, const crdt_map_mvreg_slab* slab, const crdt_read_queries* queries,
+                       size_t n_obj, uint32_t n_actors, uint32_t* d_out_n, uint64_t* d_out_clk,
+                       uint64_t* d_out_val, uint32_t out_cap, void* stream) {
+  if (!ctx || !slab || !map_actors_ok(n_actors) || !cap_ok(slab->kcap, kReadKcapMax) ||
+      !cap_ok(slab->mcap, kMapOutFactor * kMapMvregMcap) || out_cap < slab->mcap || !read_queries_ok(queries, n_obj))
+    return CRDT_EINVAL;
+  if (n_obj && (!slab->n_keys || !slab->keys || !slab->mv_n || !slab->mv_clock || !slab->mv_val)) return CRDT_EINVAL;
+  if (n_obj && queries->n_q && (!d_out_n || !d_out_clk || !d_out_val)) return CRDT_EINVAL;
+  for (const void* w : {(const void*)d_out_n, (const void*)d_out_clk, (const void*)d_out_val})
+    if (read_alias(w, queries, {slab->n_keys, slab->keys, slab->mv_n, slab->mv_clock, slab->mv_val}))
+      return CRDT_EINVAL;
+  if (n_obj == 0) return CRDT_OK;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_map_mvreg_get(*slab, *queries, n_obj, n_actors, d_out_n, d_out_clk, d_out_val, out_cap,
+                              ctx->d_status, S(stream));
+}
+
 }  // extern "C"

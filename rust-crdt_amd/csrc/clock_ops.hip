@@ -140,29 +140,8 @@ __device__ __forceinline__ void for_each_op(const uint64_t* obj_end, uint64_t n_
     b = i ? obj_end[i - 1u] : 0ull;
   }
   const bool good = b <= e && e <= n_ops;
-  const uint64_t badm = __ballot(valid && !good);
-  if (badm && lane == 0u) fail(status, CRDT_ENONCANON);
-  const uint32_t nv = (uint32_t)__popcll(__ballot(valid));  // the valid lanes are [0, nv), nv >= 1
-  const uint64_t start = lane_u64(b, 0u), span = lane_u64(e, nv - 1u) - start;
-  if (!badm && span < 0xffffffffull) {
-    // the ends ascend: op j belongs to the object after the last end <= j
-    const uint32_t T = (uint32_t)span;
-    const uint32_t rel = valid ? (uint32_t)(e - start) : T;
-    for (uint32_t base = 0; base < T; base += kW) {
-      const uint32_t jr = base + lane;
-      const bool has = jr < T;
-      const uint32_t t = rank_regs(rel, kW, (has ? jr : 0u) + 1u);
-      f(start + jr, has, t & 63u);
-    }
-  } else {
-    uint64_t run = __ballot(valid && good && e > b);
-    while (run) {
-      const uint32_t t = (uint32_t)__builtin_ctzll(run);
-      run &= run - 1u;
-      const uint64_t bb = lane_u64(b, t), ee = lane_u64(e, t);
-      for (uint64_t j0 = bb; j0 < ee; j0 += kW) f(j0 + lane, j0 + lane < ee, t);
-    }
-  }
+  if (__ballot(valid && !good) && lane == 0u) fail(status, CRDT_ENONCANON);
+  for_each_in_ranges(valid, good, b, e, lane, f);  // csr_rank.h
 }
 
 // MODE 0: VClock / GCounter apply; 1: PNCounter apply ([P|N] rows); 2: get

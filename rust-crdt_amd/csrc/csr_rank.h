@@ -43,6 +43,39 @@ __device__ __forceinline__ uint32_t rank_regs(uint32_t a, uint32_t n, uint32_t x
   return (c <= n && p < x) ? c : b;
 }
 
+// The ops (or queries) of 64 objects, flat. Lane k holds object k's range
+// [b, e) of a per-object grouped batch (b = the previous object's end), `valid`
+// where the object exists and `good` where its range ascends inside the batch.
+// Calls f(j, has, t) for every op j of the chunk: `has` says the lane holds op
+// j, t is the lane that stands for j's object. Every lane makes every call (f
+// may read across lanes). The ops of objects that are not good are skipped.
+template <class F>
+__device__ __forceinline__ void for_each_in_ranges(bool valid, bool good, uint64_t b, uint64_t e, uint32_t lane,
+                                                   F f) {
+  const uint64_t badm = __ballot(valid && !good);
+  const uint32_t nv = (uint32_t)__popcll(__ballot(valid));  // the valid lanes are [0, nv), nv >= 1
+  const uint64_t start = lane_u64(b, 0u), span = lane_u64(e, nv - 1u) - start;
+  if (!badm && span < 0xffffffffull) {
+    // the ends ascend: op j belongs to the object after the last end <= j
+    const uint32_t T = (uint32_t)span;
+    const uint32_t rel = valid ? (uint32_t)(e - start) : T;
+    for (uint32_t base = 0; base < T; base += 64u) {
+      const uint32_t jr = base + lane;
+      const bool has = jr < T;
+      const uint32_t t = rank_regs(rel, 64u, (has ? jr : 0u) + 1u);
+      f(start + jr, has, t & 63u);
+    }
+  } else {
+    uint64_t run = __ballot(valid && good && e > b);
+    while (run) {
+      const uint32_t t = (uint32_t)__builtin_ctzll(run);
+      run &= run - 1u;
+      const uint64_t bb = lane_u64(b, t), ee = lane_u64(e, t);
+      for (uint64_t j0 = bb; j0 < ee; j0 += 64u) f(j0 + lane, j0 + lane < ee, t);
+    }
+  }
+}
+
 // # of entries of the sorted run a[0, n) (in HBM) below x.
 __device__ __forceinline__ uint64_t rank_mem(const uint32_t* a, uint64_t n, uint32_t x) {
   uint64_t lo = 0, len = n;

@@ -110,6 +110,16 @@ int launch_mvreg_truncate(const uint32_t* sn, const uint64_t* sclk, const uint64
 int launch_mvreg_read_clock(const uint32_t* sn, const uint64_t* sclk, uint32_t scap, uint64_t* out, uint64_t n_obj,
                             uint32_t A, int* status, hipStream_t stream);
 
+// The read path (read.hip): exactly one of sizes / out is non-null (the sizes
+// call / the write call); the same kernel, so the two cannot disagree.
+int launch_orswot_read(const crdt_orswot_batch& B, const crdt_read_queries& Q, uint32_t A, uint32_t flags,
+                       const crdt_read_sizes* sizes, const crdt_read_out* out, int* status, hipStream_t stream);
+int launch_map_read(const crdt_map_read_view& V, const crdt_read_queries& Q, uint64_t n_obj, uint32_t A,
+                    const crdt_read_sizes* sizes, const crdt_read_out* out, int* status, hipStream_t stream);
+int launch_map_mvreg_get(const crdt_map_mvreg_slab& M, const crdt_read_queries& Q, uint64_t n_obj, uint32_t A,
+                         uint32_t* out_n, uint64_t* out_clk, uint64_t* out_val, uint32_t out_cap, int* status,
+                         hipStream_t stream);
+
 int launch_map_mvreg_merge(const crdt_map_mvreg_slab& S, const crdt_map_mvreg_slab& O, const crdt_map_mvreg_slab& R,
                            uint64_t n_obj, uint32_t A, int* status, uint32_t* ctl, hipStream_t stream, int variant = 0);
 // Map<u64, MVReg>::apply (map_apply.hip): R row i = S row i after its ops of P
