@@ -1492,6 +1492,111 @@ int crdt_map_map_to_bincode(crdt_ctx* ctx, const crdt_map_map_slab* slab, size_t
                             uint32_t actor_bytes, uint32_t key_bytes, uint32_t inner_key_bytes, uint32_t val_bytes,
                             uint8_t* d_out, const uint64_t* d_out_off, size_t out_bytes, void* stream);
 
+/* ------------------------------------------------------------------------ *
+ * LWWReg<u64, M>, batched (lwwreg.hip): FunkyCvRDT::merge, FunkyCmRDT::apply,
+ * update, a rank-order fold and the bincode codec. Reference: src/lwwreg.rs
+ * :27-32 (state), :56-66 (merge), :69-77 (apply), :104-118 (update).
+ *
+ * Layout, all device arrays, structure-of-arrays:
+ *   val[n]                    u64: the caller's interned value key, bijective
+ *                             as for MVReg values (key equality is value
+ *                             equality);
+ *   marker[n][marker_words]   u64, row-major, marker_words 1 or 2. Markers
+ *                             compare lexicographically, word 0 first (Rust
+ *                             tuple Ord; test/lwwreg.rs:39-45 uses a 2-tuple).
+ *
+ * merge(self, other) (src/lwwreg.rs:56-66):
+ *   other.marker > self.marker                  self := other, Ok;
+ *   markers equal and values differ             self unchanged, Err
+ *                                               (ConflictingMarker);
+ *   otherwise (equal marker and value included) self unchanged, Ok.
+ * update(val, marker) (:104-118) and apply(op) (:74-76) are the same rule as
+ * merging LWWReg{val, marker}: one device function serves all three.
+ *
+ * A list of ops o_1..o_k on state o_0 has the sequential meaning: an erring op
+ * changes nothing, later ops still apply, every op's Result is reported. In
+ * closed form the final state is the first element of o_0..o_k attaining the
+ * largest marker, and op i errs iff its marker equals the largest marker of
+ * o_0..o_{i-1} and its value differs from that of the first element attaining
+ * it (an exclusive prefix scan with a (+) b = b.marker > a.marker ? b : a).
+ *
+ * CONFLICTS ARE RESULTS, NOT FAULTS: an Err of the reference is reported in
+ * the call's own outputs (bitmap, counts, per-op bytes) and is never latched
+ * on the context: crdt_ctx_status stays CRDT_OK after a batch full of
+ * conflicts. Only malformed input (an obj_end out of order, a value too wide
+ * for its bincode width) latches.
+ *
+ * Every call: CRDT_EINVAL (before any device work) for a null ctx, a null
+ * required array with n > 0, a null ops struct, a null op array whose count
+ * says it is non-empty, marker_words outside {1, 2}, a byte width outside
+ * {1, 2, 4, 8}, n_reps of 0 or above 32, a null view pointer, and an output
+ * pointer equal to an input it must not alias (self equal to other in merge,
+ * out equal to a replica other than replica 0 in fold, an op array equal to a
+ * state array in apply, blobs equal to a state array in the codec).
+ * Otherwise n == 0 is CRDT_OK, launches nothing and writes nothing, null
+ * arrays included.
+ *
+ * crdt_lwwreg_merge: self[i].merge(other[i]), in place on self.
+ *   d_conflict   u64[(n + 63) / 64], nullable: bit i % 64 of word i / 64 is set
+ *                iff register i's merge returned Err. Every word is written,
+ *                tail bits are zero.
+ *   d_n_conflict one u64, nullable: overwritten with the number of conflicts.
+ *   Both may be null. 16-byte aligned arrays take 16-byte loads and stores.
+ *
+ * crdt_lwwreg_apply: register i applies ops [obj_end[i-1], obj_end[i]) in
+ * order, in place (the obj_end convention of crdt_clock_ops).
+ *   d_n_err[i]   u32, required: the number of register i's ops that returned
+ *                Err; written for every i, 0 for an empty list.
+ *   d_op_err[j]  u8, nullable: op j's Result, 0 Ok, 1 Err.
+ *   An object whose range decreases or runs past n_ops latches
+ *   CRDT_ENONCANON: it is left untouched with d_n_err[i] = 0 (its ops' bytes
+ *   of d_op_err are not written), the other objects apply; nothing outside
+ *   the op arrays is read. Lists shorter than CRDT_LWWREG_WAVE_MIN_OPS are
+ *   applied by one lane each, longer ones by a wave in chunks of 64 ops.
+ *
+ * crdt_lwwreg_fold: out[i] = reps[0][i].merge(reps[1][i]).merge(reps[2][i])...
+ * in rank order (the fixed-order convention of crdt_orswot_fold), one pass:
+ * every replica's state is read once, the output written once. h_reps is a
+ * HOST array of n_reps views, 1 <= n_reps <= 32. d_n_err[i] (u32, nullable)
+ * counts the erring merges of register i. The output may be replica 0's
+ * arrays (in place), never another replica's.
+ *
+ * crdt_lwwreg_from_bincode / crdt_lwwreg_to_bincode: to_binary of
+ * LWWReg<V, M> is the struct's fields in order (src/lwwreg.rs:27-32): val,
+ * then the marker words, each fixed-width little-endian. So a blob has the
+ * constant size val_bytes + marker_bytes0 (+ marker_bytes1 with two marker
+ * words; ignored with one) and no sizes call exists. Blob i is at d_blobs +
+ * i * stride, at any alignment; stride below the blob size is CRDT_EINVAL.
+ * Ingest widens to u64. Egest narrows: a value or marker word that does not
+ * fit its width latches CRDT_ENONCANON, that blob is not written, the others
+ * are. Bytes between a blob's end and the next stride are never touched.
+ * ------------------------------------------------------------------------ */
+#define CRDT_LWWREG_WAVE_MIN_OPS 16  /* shortest op list the wave-per-register form of crdt_lwwreg_apply takes */
+#define CRDT_LWWREG_MAX_REPS 32
+typedef struct crdt_lwwreg_ops {   /* all device arrays */
+  const uint64_t* obj_end;  /* n_obj: register i's ops are [obj_end[i-1], obj_end[i]) */
+  const uint64_t* val;      /* n_ops */
+  const uint64_t* marker;   /* n_ops x marker_words */
+  size_t n_ops;
+} crdt_lwwreg_ops;
+typedef struct crdt_lwwreg_view {  /* one replica's registers, device arrays */
+  const uint64_t* val;
+  const uint64_t* marker;
+} crdt_lwwreg_view;
+int crdt_lwwreg_merge(crdt_ctx* ctx, uint64_t* d_self_val, uint64_t* d_self_marker, const uint64_t* d_other_val,
+                      const uint64_t* d_other_marker, size_t n, uint32_t marker_words, uint64_t* d_conflict,
+                      uint64_t* d_n_conflict, void* stream);
+int crdt_lwwreg_apply(crdt_ctx* ctx, uint64_t* d_self_val, uint64_t* d_self_marker, const crdt_lwwreg_ops* ops,
+                      size_t n_obj, uint32_t marker_words, uint32_t* d_n_err, uint8_t* d_op_err, void* stream);
+int crdt_lwwreg_fold(crdt_ctx* ctx, const crdt_lwwreg_view* h_reps, uint32_t n_reps, size_t n, uint32_t marker_words,
+                     uint64_t* d_out_val, uint64_t* d_out_marker, uint32_t* d_n_err, void* stream);
+int crdt_lwwreg_from_bincode(crdt_ctx* ctx, const uint8_t* d_blobs, size_t stride, size_t n, uint32_t val_bytes,
+                             uint32_t marker_words, uint32_t marker_bytes0, uint32_t marker_bytes1,
+                             uint64_t* d_out_val, uint64_t* d_out_marker, void* stream);
+int crdt_lwwreg_to_bincode(crdt_ctx* ctx, const uint64_t* d_val, const uint64_t* d_marker, size_t n,
+                           uint32_t val_bytes, uint32_t marker_words, uint32_t marker_bytes0, uint32_t marker_bytes1,
+                           uint8_t* d_blobs, size_t stride, void* stream);
+
 /* Dense synthetic counters: u64[n_obj][n_actors] rows for objects
  * [first_obj, first_obj+n_obj), counter U[0, 2^bits) with `pct_zero` % zeros. */
 int crdt_dense_generate(uint64_t seed, size_t first_obj, size_t n_obj, uint32_t n_actors,

@@ -19,6 +19,7 @@ import numpy as np
 
 from ._lib import (CRDT_COMM_ID_BYTES, CRDT_ECAPACITY, CRDT_EINVAL, CRDT_ENONCANON, CRDT_OK, EXPORTS, LIB_PATH, SPARSE_CLOCK, Batch, CrdtError,
                    GenParams, RepParams, check, lib)
+from .lwwreg import (LWWREG_MAX_REPS, LWWREG_WAVE_MIN_OPS, ConflictingMarker, LWWBatch, LWWEngine, LWWOps, LWWReg)
 from .record import decode_record, encode_record, record_bytes
 
 __all__ = [
@@ -26,7 +27,7 @@ __all__ = [
     "Orswot", "VClock", "GCounter", "PNCounter", "merge_batch", "decode_record", "encode_record",
     "record_bytes", "CONFIG3", "EXPORTS", "LIB_PATH", "CONFIG5", "SPARSE_CLOCK", "generate_replicas", "ClockBatch",
     "generate_clocks_csr", "MapMapSlab", "MapOps", "MapMapOps", "MVRegOps", "ClockOps",
-    "ReadQueries",
+    "ReadQueries", "LWWReg", "LWWBatch", "LWWOps", "ConflictingMarker", "LWWREG_WAVE_MIN_OPS", "LWWREG_MAX_REPS",
 ]
 
 # SURVEY.md §8(d) config 3 / BASELINE.json configs[2].
@@ -888,8 +889,9 @@ class MapOrswotSlab:
         return _read_view(self.a, self.caps["kcap"])
 
 
-class Engine:
-    """One crdt_ctx bound to a device. All merges run on the GPU."""
+class Engine(LWWEngine):
+    """One crdt_ctx bound to a device. All merges run on the GPU (the LWWReg
+    calls live in lwwreg.py)."""
 
     def __init__(self, device=0):
         torch = _torch()

@@ -91,6 +91,8 @@ EXPORTS = [
     "crdt_vclock_dense_get", "crdt_vclock_csr_truncate", "crdt_vclock_csr_subtract", "crdt_vclock_csr_intersection",
     "crdt_vclock_csr_apply", "crdt_gcounter_csr_apply", "crdt_gcounter_csr_value", "crdt_vclock_csr_get",
     "crdt_orswot_read_sizes", "crdt_orswot_read", "crdt_map_read_sizes", "crdt_map_read", "crdt_map_mvreg_get",
+    "crdt_lwwreg_merge", "crdt_lwwreg_apply", "crdt_lwwreg_fold", "crdt_lwwreg_from_bincode",
+    "crdt_lwwreg_to_bincode",
 ]
 
 CRDT_COMM_ID_BYTES = 128
@@ -180,6 +182,16 @@ class ClockCsr(C.Structure):
 class ClockOpsC(C.Structure):
     """crdt_clock_ops (include/crdts_hip.h)."""
     _fields_ = [(f, C.c_void_p) for f in ("obj_end", "actor", "counter", "dir")] + [("n_ops", C.c_size_t)]
+
+
+class LWWOpsC(C.Structure):
+    """crdt_lwwreg_ops (include/crdts_hip.h)."""
+    _fields_ = [(f, C.c_void_p) for f in ("obj_end", "val", "marker")] + [("n_ops", C.c_size_t)]
+
+
+class LWWViewC(C.Structure):
+    """crdt_lwwreg_view (include/crdts_hip.h)."""
+    _fields_ = [("val", C.c_void_p), ("marker", C.c_void_p)]
 
 
 class ReadQueriesC(C.Structure):
@@ -358,6 +370,11 @@ def _load():
                                     C.POINTER(ReadSizesC), P]),
         "crdt_map_read": (I, [P, C.POINTER(MapReadViewC), C.POINTER(ReadQueriesC), SZ, U32, C.POINTER(ReadOutC), P]),
         "crdt_map_mvreg_get": (I, [P, C.POINTER(MapSlabC), C.POINTER(ReadQueriesC), SZ, U32, P, P, P, U32, P]),
+        "crdt_lwwreg_merge": (I, [P, P, P, P, P, SZ, U32, P, P, P]),
+        "crdt_lwwreg_apply": (I, [P, P, P, C.POINTER(LWWOpsC), SZ, U32, P, P, P]),
+        "crdt_lwwreg_fold": (I, [P, C.POINTER(LWWViewC), U32, SZ, U32, P, P, P, P]),
+        "crdt_lwwreg_from_bincode": (I, [P, P, SZ, SZ, U32, U32, U32, U32, P, P, P]),
+        "crdt_lwwreg_to_bincode": (I, [P, P, P, SZ, U32, U32, U32, U32, P, SZ, P]),
         "crdt_orswot_generate_replicas_subset": (I, [U64, SZ, SZ, C.POINTER(RepParams), U32, U32, U32, U32, I,
                                                      C.POINTER(P)]),
         "crdt_orswot_replica_join_transport": (I, [P, C.POINTER(TransportC), BP, U32, U32, P, P, SZ, C.POINTER(SZ),

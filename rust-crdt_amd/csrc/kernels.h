@@ -110,6 +110,20 @@ int launch_mvreg_truncate(const uint32_t* sn, const uint64_t* sclk, const uint64
 int launch_mvreg_read_clock(const uint32_t* sn, const uint64_t* sclk, uint32_t scap, uint64_t* out, uint64_t n_obj,
                             uint32_t A, int* status, hipStream_t stream);
 
+// LWWReg (lwwreg.hip; the ABI functions validate there too). marker_words is
+// 1 or 2; merge's bitmap / count and fold's / apply's op_err may be null.
+int launch_lwwreg_merge(uint64_t* sval, uint64_t* smark, const uint64_t* oval, const uint64_t* omark, uint64_t n,
+                        uint32_t marker_words, uint64_t* bitmap, uint64_t* count, hipStream_t stream);
+int launch_lwwreg_apply(uint64_t* sval, uint64_t* smark, const crdt_lwwreg_ops& P, uint64_t n_obj,
+                        uint32_t marker_words, uint32_t* n_err, uint8_t* op_err, int* status, hipStream_t stream);
+int launch_lwwreg_fold(const crdt_lwwreg_view* reps, uint32_t n_reps, uint64_t n, uint32_t marker_words,
+                       uint64_t* oval, uint64_t* omark, uint32_t* n_err, hipStream_t stream);
+int launch_lwwreg_from_bincode(const uint8_t* blobs, uint64_t stride, uint64_t n, uint32_t vb, uint32_t marker_words,
+                               uint32_t mb0, uint32_t mb1, uint64_t* val, uint64_t* marker, hipStream_t stream);
+int launch_lwwreg_to_bincode(const uint64_t* val, const uint64_t* marker, uint64_t n, uint32_t vb,
+                             uint32_t marker_words, uint32_t mb0, uint32_t mb1, uint8_t* blobs, uint64_t stride,
+                             int* status, hipStream_t stream);
+
 // The read path (read.hip): exactly one of sizes / out is non-null (the sizes
 // call / the write call); the same kernel, so the two cannot disagree.
 int launch_orswot_read(const crdt_orswot_batch& B, const crdt_read_queries& Q, uint32_t A, uint32_t flags,
