@@ -1597,6 +1597,105 @@ int crdt_lwwreg_to_bincode(crdt_ctx* ctx, const uint64_t* d_val, const uint64_t*
                            uint32_t val_bytes, uint32_t marker_words, uint32_t marker_bytes0, uint32_t marker_bytes1,
                            uint8_t* d_blobs, size_t stride, void* stream);
 
+/* ------------------------------------------------------------------------ *
+ * bincode of the clocks, the counters and their ops (clock_bincode.hip):
+ * `to_binary` / `from_binary` (src/lib.rs:62-83) of VClock, GCounter and
+ * PNCounter states, on dense rows and on CSR runs, and of their CmRDT ops.
+ *
+ * Wire format (bincode 0.9 of the serde derives; A = an unsigned integer of
+ * actor_bytes in {1, 2, 4, 8}, little-endian, taken as the interned actor id):
+ *   VClock<A>     u64 n | n x (A actor | u64 counter), actors strictly
+ *                 ascending (a BTreeMap, src/vclock.rs:53-57)
+ *   GCounter<A>   its `inner` VClock (src/gcounter.rs:26-28): the same bytes
+ *   PNCounter<A>  VClock p | VClock n (src/pncounter.rs:33-36)
+ *   Dot<A>        A actor | u64 counter (src/vclock.rs:33-39): the Op of
+ *                 VClock and GCounter, actor_bytes + 8 bytes
+ *   PNCounter Op  Dot | u32 variant index of Dir, Pos = 0, Neg = 1
+ *                 (src/pncounter.rs:39-56): actor_bytes + 12 bytes
+ * BTreeMap order makes the bytes of a state unique: ingest reorders nothing
+ * and egest has one answer. (The reference's tests assert no bytes: parity
+ * unpinned by reference output.)
+ *
+ * State blob i is [d_blob_off[i], d_blob_off[i] + d_blob_len[i]) of d_blobs,
+ * at any alignment. n_clocks is 1 for VClock / GCounter, 2 for PNCounter.
+ * Nothing outside a blob's aligned 16-byte lines within d_blobs is read.
+ *
+ * Dense rows (the layout of crdt_vclock_dense_merge; PNCounter: the [P|N] row
+ * of 2 * n_actors slots):
+ *   crdt_clock_dense_from_bincode writes every slot of every row (absent
+ *     actors 0; each row leaves the chip once, in full-width stores).
+ *   crdt_clock_dense_bincode_sizes: d_sizes[i] = 8 * n_clocks + (nonzero
+ *     slots of row i) * (actor_bytes + 8).
+ *   crdt_clock_dense_to_bincode writes blob i at d_out + d_out_off[i], any
+ *     byte offset (the caller places the blobs, e.g. by an exclusive scan of
+ *     the sizes); no byte outside the blobs is written.
+ * CSR runs (crdt_clock_csr / crdt_clock_csr_out; PNCounter: two batches as in
+ * crdt_pncounter_csr_merge; the _n arguments are null when n_clocks == 1):
+ *   crdt_clock_csr_bincode_lens: the entry counts of every blob, from its
+ *     framing alone (each length word against the bytes left, and the exact
+ *     blob length); a blob with bad framing gets 0 and is latched.
+ *   crdt_clock_csr_from_bincode: HERE out.off IS AN INPUT — the caller places
+ *     the runs (e.g. an exclusive scan of the lens; gaps are fine); out.len
+ *     and the entries are written. A run placed past out.n_entries latches
+ *     CRDT_ECAPACITY (len 0). The output is a valid (gapped) input batch of
+ *     every crdt_*_csr_* call when the caller's offsets ascend.
+ *   crdt_clock_csr_bincode_sizes / crdt_clock_csr_to_bincode: as the dense
+ *     pair; self_n null selects one clock per object.
+ * Ops: fixed-size blobs, op j at d_blobs + j * stride, at any alignment (as
+ * in the LWWReg codec); with_dir != 0 selects the PNCounter Op.
+ *   crdt_clock_ops_from_bincode fills the actor / counter / dir arrays of a
+ *     crdt_clock_ops (obj_end stays the caller's: grouping is not on the
+ *     wire); d_dir is not touched without with_dir.
+ *   crdt_clock_ops_to_bincode: bytes between a blob's end and the next
+ *     stride are never touched.
+ *
+ * Latched per object (crdt_ctx_status), the other objects unaffected:
+ *   CRDT_ENONCANON on ingest: a zero counter; actors not strictly ascending
+ *     (or duplicated); an actor >= n_actors (dense) or >= 2^32 (CSR, ops); a
+ *     blob that ends early or has trailing bytes; a length word larger than
+ *     the bytes left can hold (checked before any multiply) or than any
+ *     canonical clock; a blob not inside d_blobs; a PNCounter whose p runs to
+ *     or past the blob's end; an op whose Dir index is above 1 (all four
+ *     bytes are compared). A bad dense object's row is all zero, a bad CSR
+ *     object has len 0 (both clocks of a PNCounter), a bad op becomes actor
+ *     0xFFFFFFFF, counter 0, dir 0, which every apply skips and latches.
+ *   CRDT_ENONCANON on egest (size 0, nothing written): an actor id with a
+ *     non-zero counter that does not fit actor_bytes; a CSR run that is not
+ *     canonical (actors not strictly ascending, a zero counter) or lies
+ *     outside [0, n_entries); an op dir above 1.
+ *   CRDT_ECAPACITY on egest: a blob placed past out_bytes (not written).
+ * CRDT_EINVAL (before any device work): a null ctx; a null array (or struct)
+ * with a non-zero count; a width outside {1, 2, 4, 8}; n_actors == 0;
+ * n_clocks outside {1, 2}; self_n->n_obj != self_p->n_obj; a stride below
+ * the op size; an output array equal to an input array. Otherwise zero
+ * objects / ops is CRDT_OK and launches nothing. Clocks of any length.
+ * ------------------------------------------------------------------------ */
+int crdt_clock_dense_from_bincode(crdt_ctx* ctx, const uint8_t* d_blobs, size_t blob_bytes, const uint64_t* d_blob_off,
+                                  const uint64_t* d_blob_len, size_t n_obj, uint32_t actor_bytes, uint32_t n_actors,
+                                  uint32_t n_clocks, uint64_t* d_rows, void* stream);
+int crdt_clock_dense_bincode_sizes(crdt_ctx* ctx, const uint64_t* d_rows, size_t n_obj, uint32_t n_actors,
+                                   uint32_t n_clocks, uint32_t actor_bytes, uint64_t* d_sizes, void* stream);
+int crdt_clock_dense_to_bincode(crdt_ctx* ctx, const uint64_t* d_rows, size_t n_obj, uint32_t n_actors,
+                                uint32_t n_clocks, uint32_t actor_bytes, uint8_t* d_out, const uint64_t* d_out_off,
+                                size_t out_bytes, void* stream);
+int crdt_clock_csr_bincode_lens(crdt_ctx* ctx, const uint8_t* d_blobs, size_t blob_bytes, const uint64_t* d_blob_off,
+                                const uint64_t* d_blob_len, size_t n_obj, uint32_t actor_bytes, uint32_t n_clocks,
+                                uint32_t* d_len_p, uint32_t* d_len_n, void* stream);
+int crdt_clock_csr_from_bincode(crdt_ctx* ctx, const uint8_t* d_blobs, size_t blob_bytes, const uint64_t* d_blob_off,
+                                const uint64_t* d_blob_len, size_t n_obj, uint32_t actor_bytes, uint32_t n_clocks,
+                                const crdt_clock_csr_out* out_p, const crdt_clock_csr_out* out_n, void* stream);
+int crdt_clock_csr_bincode_sizes(crdt_ctx* ctx, const crdt_clock_csr* self_p, const crdt_clock_csr* self_n,
+                                 uint32_t actor_bytes, uint64_t* d_sizes, void* stream);
+int crdt_clock_csr_to_bincode(crdt_ctx* ctx, const crdt_clock_csr* self_p, const crdt_clock_csr* self_n,
+                              uint32_t actor_bytes, uint8_t* d_out, const uint64_t* d_out_off, size_t out_bytes,
+                              void* stream);
+int crdt_clock_ops_from_bincode(crdt_ctx* ctx, const uint8_t* d_blobs, size_t stride, size_t n_ops,
+                                uint32_t actor_bytes, uint32_t with_dir, uint32_t* d_actor, uint64_t* d_counter,
+                                uint32_t* d_dir, void* stream);
+int crdt_clock_ops_to_bincode(crdt_ctx* ctx, const uint32_t* d_actor, const uint64_t* d_counter,
+                              const uint32_t* d_dir, size_t n_ops, uint32_t actor_bytes, uint32_t with_dir,
+                              uint8_t* d_blobs, size_t stride, void* stream);
+
 /* Dense synthetic counters: u64[n_obj][n_actors] rows for objects
  * [first_obj, first_obj+n_obj), counter U[0, 2^bits) with `pct_zero` % zeros. */
 int crdt_dense_generate(uint64_t seed, size_t first_obj, size_t n_obj, uint32_t n_actors,

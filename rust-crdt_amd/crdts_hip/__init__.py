@@ -19,6 +19,7 @@ import numpy as np
 
 from ._lib import (CRDT_COMM_ID_BYTES, CRDT_ECAPACITY, CRDT_EINVAL, CRDT_ENONCANON, CRDT_OK, EXPORTS, LIB_PATH, SPARSE_CLOCK, Batch, CrdtError,
                    GenParams, RepParams, check, lib)
+from .clock_bincode import ClockBincodeEngine
 from .lwwreg import (LWWREG_MAX_REPS, LWWREG_WAVE_MIN_OPS, ConflictingMarker, LWWBatch, LWWEngine, LWWOps, LWWReg)
 from .record import decode_record, encode_record, record_bytes
 
@@ -401,6 +402,32 @@ class ClockOps:
     def from_lists(cls, per_obj, with_dir=False, device=0):
         """per_obj[i] = object i's dots, see arrays_from_lists."""
         return cls.from_arrays(*cls.arrays_from_lists(per_obj, with_dir), device=device)
+
+    @classmethod
+    def from_bincode(cls, blobs, stride, obj_end, actor_bytes, with_dir=False, engine=None, stream=None,
+                     check_status=True):
+        """Op blobs as they travel between replicas — Dot<A> (src/vclock.rs:33-39),
+        or PNCounter's Op with with_dir (src/pncounter.rs:39-56) — at blobs[j *
+        stride] (uint8 device tensor; stride None: the op size) -> ClockOps.
+        obj_end (int64 device tensor, or a host array) groups them: grouping is
+        not on the wire. A malformed op becomes the sentinel every apply skips
+        and latches (CRDT_ENONCANON here too)."""
+        torch = _torch()
+        engine = engine or default_engine()
+        if not torch.is_tensor(obj_end):
+            obj_end = torch.from_numpy(np.ascontiguousarray(np.asarray(obj_end, np.uint64)).view(np.int64)).to(
+                blobs.device)
+        n_ops = int(obj_end[-1].item()) if obj_end.numel() else 0
+        actor, counter, dir_ = engine.clock_ops_from_bincode(blobs, n_ops, actor_bytes, with_dir, stride, stream,
+                                                             check_status)
+        return cls(obj_end, actor, counter, dir_)
+
+    def to_bincode(self, actor_bytes, stride=None, out=None, engine=None, stream=None, check_status=True):
+        """The ops' wire form: a uint8 device tensor, op j at [j * stride]
+        (PNCounter's Op when the batch carries dir)."""
+        engine = engine or default_engine()
+        _, actor, counter, dir_ = self.t
+        return engine.clock_ops_to_bincode(actor, counter, dir_, actor_bytes, stride, out, stream, check_status)
 
 
 class ReadQueries:
@@ -889,7 +916,7 @@ class MapOrswotSlab:
         return _read_view(self.a, self.caps["kcap"])
 
 
-class Engine(LWWEngine):
+class Engine(LWWEngine, ClockBincodeEngine):
     """One crdt_ctx bound to a device. All merges run on the GPU (the LWWReg
     calls live in lwwreg.py)."""
 

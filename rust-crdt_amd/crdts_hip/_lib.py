@@ -93,6 +93,9 @@ EXPORTS = [
     "crdt_orswot_read_sizes", "crdt_orswot_read", "crdt_map_read_sizes", "crdt_map_read", "crdt_map_mvreg_get",
     "crdt_lwwreg_merge", "crdt_lwwreg_apply", "crdt_lwwreg_fold", "crdt_lwwreg_from_bincode",
     "crdt_lwwreg_to_bincode",
+    "crdt_clock_dense_from_bincode", "crdt_clock_dense_bincode_sizes", "crdt_clock_dense_to_bincode",
+    "crdt_clock_csr_bincode_lens", "crdt_clock_csr_from_bincode", "crdt_clock_csr_bincode_sizes",
+    "crdt_clock_csr_to_bincode", "crdt_clock_ops_from_bincode", "crdt_clock_ops_to_bincode",
 ]
 
 CRDT_COMM_ID_BYTES = 128
@@ -375,6 +378,16 @@ def _load():
         "crdt_lwwreg_fold": (I, [P, C.POINTER(LWWViewC), U32, SZ, U32, P, P, P, P]),
         "crdt_lwwreg_from_bincode": (I, [P, P, SZ, SZ, U32, U32, U32, U32, P, P, P]),
         "crdt_lwwreg_to_bincode": (I, [P, P, P, SZ, U32, U32, U32, U32, P, SZ, P]),
+        "crdt_clock_dense_from_bincode": (I, [P, P, SZ, P, P, SZ, U32, U32, U32, P, P]),
+        "crdt_clock_dense_bincode_sizes": (I, [P, P, SZ, U32, U32, U32, P, P]),
+        "crdt_clock_dense_to_bincode": (I, [P, P, SZ, U32, U32, U32, P, P, SZ, P]),
+        "crdt_clock_csr_bincode_lens": (I, [P, P, SZ, P, P, SZ, U32, U32, P, P, P]),
+        "crdt_clock_csr_from_bincode": (I, [P, P, SZ, P, P, SZ, U32, U32, C.POINTER(ClockCsrOut),
+                                            C.POINTER(ClockCsrOut), P]),
+        "crdt_clock_csr_bincode_sizes": (I, [P, C.POINTER(ClockCsr), C.POINTER(ClockCsr), U32, P, P]),
+        "crdt_clock_csr_to_bincode": (I, [P, C.POINTER(ClockCsr), C.POINTER(ClockCsr), U32, P, P, SZ, P]),
+        "crdt_clock_ops_from_bincode": (I, [P, P, SZ, SZ, U32, U32, P, P, P, P]),
+        "crdt_clock_ops_to_bincode": (I, [P, P, P, P, SZ, U32, U32, P, SZ, P]),
         "crdt_orswot_generate_replicas_subset": (I, [U64, SZ, SZ, C.POINTER(RepParams), U32, U32, U32, U32, I,
                                                      C.POINTER(P)]),
         "crdt_orswot_replica_join_transport": (I, [P, C.POINTER(TransportC), BP, U32, U32, P, P, SZ, C.POINTER(SZ),

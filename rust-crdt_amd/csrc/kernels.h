@@ -124,6 +124,33 @@ int launch_lwwreg_to_bincode(const uint64_t* val, const uint64_t* marker, uint64
                              uint32_t marker_words, uint32_t mb0, uint32_t mb1, uint8_t* blobs, uint64_t stride,
                              int* status, hipStream_t stream);
 
+// bincode codec of the clocks, the counters and their ops (clock_bincode.hip;
+// the ABI functions validate there too). ab: actor bytes in {1, 2, 4, 8}; nc:
+// clocks per object (1, or 2: PNCounter). Egest: out == nullptr is the sizes
+// pass; self_n == nullptr is one clock per object.
+int launch_clock_dense_from_bincode(const uint8_t* blobs, uint64_t blob_bytes, const uint64_t* boff,
+                                    const uint64_t* blen, uint64_t n_obj, uint32_t ab, uint32_t A, uint32_t nc,
+                                    uint64_t* rows, int* status, hipStream_t stream);
+int launch_clock_dense_to_bincode(const uint64_t* rows, uint64_t n_obj, uint32_t A, uint32_t nc, uint32_t ab,
+                                  uint64_t* sizes, uint8_t* out, const uint64_t* ooff, uint64_t out_bytes,
+                                  int* status, hipStream_t stream);
+int launch_clock_csr_bincode_lens(const uint8_t* blobs, uint64_t blob_bytes, const uint64_t* boff,
+                                  const uint64_t* blen, uint64_t n_obj, uint32_t ab, uint32_t nc, uint32_t* len_p,
+                                  uint32_t* len_n, int* status, hipStream_t stream);
+int launch_clock_csr_from_bincode(const uint8_t* blobs, uint64_t blob_bytes, const uint64_t* boff,
+                                  const uint64_t* blen, uint64_t n_obj, uint32_t ab, uint32_t nc,
+                                  const crdt_clock_csr_out* out_p, const crdt_clock_csr_out* out_n, int* status,
+                                  hipStream_t stream);
+int launch_clock_csr_to_bincode(const crdt_clock_csr* self_p, const crdt_clock_csr* self_n, uint32_t ab,
+                                uint64_t* sizes, uint8_t* out, const uint64_t* ooff, uint64_t out_bytes, int* status,
+                                hipStream_t stream);
+int launch_clock_ops_from_bincode(const uint8_t* blobs, uint64_t stride, uint64_t n_ops, uint32_t ab, bool with_dir,
+                                  uint32_t* actor, uint64_t* counter, uint32_t* dir, int* status,
+                                  hipStream_t stream);
+int launch_clock_ops_to_bincode(const uint32_t* actor, const uint64_t* counter, const uint32_t* dir, uint64_t n_ops,
+                                uint32_t ab, bool with_dir, uint8_t* blobs, uint64_t stride, int* status,
+                                hipStream_t stream);
+
 // The read path (read.hip): exactly one of sizes / out is non-null (the sizes
 // call / the write call); the same kernel, so the two cannot disagree.
 int launch_orswot_read(const crdt_orswot_batch& B, const crdt_read_queries& Q, uint32_t A, uint32_t flags,
