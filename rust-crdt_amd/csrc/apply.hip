@@ -26,9 +26,12 @@
 #include "kernels.h"
 #include "sched.h"
 #include "record_layout.h"
+#include "wave.h"
 
 namespace crdts_hip {
 namespace {
+
+using namespace wave;  // sync, uni32 / uni64, lane32 / lane64, shfl64 (wave.h)
 
 constexpr uint32_t kAW = 64;
 // Workspace capacities. Every object is first run in the small workspace
@@ -79,29 +82,12 @@ struct Cnt {
   uint32_t clk, mem, dot, def, fdot, fmem, tmp;
 };
 
-// hand-off between the lanes of the wave through the workspace: LDS, or
-// (G) HBM, whose stores must have completed before another lane reads
-template <bool G = false>
-__device__ __forceinline__ void ap_sync() {
-  if constexpr (G) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  } else {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  }
-}
-__device__ __forceinline__ uint32_t ap_uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ uint64_t ap_uni64(uint64_t v) {
-  return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32) |
-         (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v);
-}
+// sync<G>(): the hand-off between the lanes of the wave through the workspace,
+// LDS or (G) HBM
 __device__ __forceinline__ uint32_t ap_count(bool p) { return (uint32_t)__popcll(__ballot(p)); }
 __device__ __forceinline__ uint32_t ap_sum(uint32_t v) {
   for (uint32_t d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, kAW);
-  return ap_uni(v);
+  return uni32(v);
 }
 
 // a[pos..n) -> a[pos+cnt..n+cnt): chunks from the top, so no chunk's stores
@@ -115,7 +101,7 @@ __device__ void ins_gap(T* a, uint32_t n, uint32_t pos, uint32_t cnt, uint32_t l
       a[i + cnt] = v;
     }
   }
-  ap_sync<G>();
+  sync<G>();
 }
 // a[pos+cnt..n) -> a[pos..n-cnt)
 template <bool G = false, class T>
@@ -127,12 +113,12 @@ __device__ void del_gap(T* a, uint32_t n, uint32_t pos, uint32_t cnt, uint32_t l
       a[i] = v;
     }
   }
-  ap_sync<G>();
+  sync<G>();
 }
 template <bool G = false, class T>
 __device__ void add_range(T* a, uint32_t b, uint32_t e, T d, uint32_t lane) {
   for (uint32_t i = b + lane; i < e; i += kAW) a[i] += d;
-  ap_sync<G>();
+  sync<G>();
 }
 // # of a[b..e) < x (a sorted or not: a plain count)
 template <class T>
@@ -182,11 +168,11 @@ __device__ void entry_subtract(Ws<C>& w, Cnt& c, uint64_t m, uint32_t lane) {
       if (h) { x = w.dact[b + base + lane]; v = w.dctr[b + base + lane]; }
       const bool k = h && !(list_get(w.tact, w.tctr, c.tmp, x) >= v);
       const uint64_t K = __ballot(k);
-      ap_sync<C::kG>();
+      sync<C::kG>();
       const uint32_t r = kept + __builtin_amdgcn_mbcnt_hi((uint32_t)(K >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)K, 0u));
       if (k && kept + (uint32_t)__popcll(K) < n + 1u) { w.dact[b + r] = x; w.dctr[b + r] = v; }
       kept += (uint32_t)__popcll(K);
-      ap_sync<C::kG>();
+      sync<C::kG>();
     }
     if (kept == n) return;
   } else {
@@ -201,13 +187,13 @@ __device__ void entry_subtract(Ws<C>& w, Cnt& c, uint64_t m, uint32_t lane) {
     const uint64_t K0 = __ballot(k0), K1 = __ballot(k1);
     kept = (uint32_t)__popcll(K0) + (uint32_t)__popcll(K1);
     if (kept == n) return;
-    ap_sync<C::kG>();
+    sync<C::kG>();
     const uint32_t r0 = __builtin_amdgcn_mbcnt_hi((uint32_t)(K0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)K0, 0u));
     const uint32_t r1 = (uint32_t)__popcll(K0) +
                         __builtin_amdgcn_mbcnt_hi((uint32_t)(K1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)K1, 0u));
     if (k0) { w.dact[b + r0] = x0; w.dctr[b + r0] = v0; }
     if (k1) { w.dact[b + r1] = x1; w.dctr[b + r1] = v1; }
-    ap_sync<C::kG>();
+    sync<C::kG>();
   }
   const uint32_t drop = n - kept;
   del_gap<C::kG>(w.dact, c.dot, b + kept, drop, lane);
@@ -259,7 +245,7 @@ __device__ int deferred_add(Ws<C>& w, Cnt& c, uint64_t m, uint32_t lane) {
     if (c.fmem + 1u > C::kFMem) return CRDT_ECAPACITY;
     ins_gap<C::kG>(w.fkey, c.fmem, ms + r, 1u, lane);
     if (lane == 0u) w.fkey[ms + r] = m;
-    ap_sync<C::kG>();
+    sync<C::kG>();
     add_range<C::kG>(w.fmend, k, c.def, 1u, lane);
     c.fmem += 1u;
     return 0;
@@ -274,7 +260,7 @@ __device__ int deferred_add(Ws<C>& w, Cnt& c, uint64_t m, uint32_t lane) {
   ins_gap<C::kG>(w.fdend, c.def, kk, 1u, lane);
   ins_gap<C::kG>(w.fmend, c.def, kk, 1u, lane);
   if (lane == 0u) { w.fdend[kk] = o + c.tmp; w.fmend[kk] = om + 1u; }
-  ap_sync<C::kG>();
+  sync<C::kG>();
   add_range<C::kG>(w.fdend, kk + 1u, c.def + 1u, c.tmp, lane);
   add_range<C::kG>(w.fmend, kk + 1u, c.def + 1u, 1u, lane);
   c.def += 1u;
@@ -292,11 +278,11 @@ __device__ void apply_deferred(Ws<C>& w, Cnt& c, bool sparse, uint32_t lane) {
     const uint32_t ms = k ? w.fmend[k - 1] : 0u, me = w.fmend[k];
     for (uint32_t i = lane; i < e - b; i += kAW) { w.tact[i] = w.fact[b + i]; w.tctr[i] = w.fctr[b + i]; }
     c.tmp = e - b;
-    ap_sync<C::kG>();
+    sync<C::kG>();
     for (uint32_t j = ms; j < me; ++j) entry_subtract(w, c, w.fkey[j], lane);
     const bool applied = tmp_le_clock(w, c, sparse, lane);
     if (lane == 0u) w.dead[k] = applied ? 1u : 0u;
-    ap_sync<C::kG>();
+    sync<C::kG>();
   }
   for (int32_t k = (int32_t)c.def - 1; k >= 0; --k) {  // drop the applied ones (top down keeps indices valid)
     if (!w.dead[k]) continue;
@@ -327,7 +313,7 @@ __device__ int op_add(Ws<C>& w, Cnt& c, bool sparse, uint32_t A, uint32_t a, uin
   } else {
     cur = w.cctr[a];
   }
-  cur = ap_uni64(cur);
+  cur = uni64(cur);
   if (cur >= ctr) return 0;  // already seen
   // entries[m] (inserted empty when absent) .witness(dot)
   uint32_t pos = count_less(w.key, 0u, c.mem, m, lane);
@@ -337,7 +323,7 @@ __device__ int op_add(Ws<C>& w, Cnt& c, bool sparse, uint32_t A, uint32_t a, uin
     ins_gap<C::kG>(w.key, c.mem, pos, 1u, lane);
     ins_gap<C::kG>(w.dend, c.mem, pos, 1u, lane);
     if (lane == 0u) { w.key[pos] = m; w.dend[pos] = at; }
-    ap_sync<C::kG>();
+    sync<C::kG>();
     c.mem += 1u;
   }
   const uint32_t b = pos ? w.dend[pos - 1] : 0u, e = w.dend[pos];
@@ -345,13 +331,13 @@ __device__ int op_add(Ws<C>& w, Cnt& c, bool sparse, uint32_t A, uint32_t a, uin
   if (C::kCk <= 2u * kAW && e - b + 1u > 2u * kAW) return CRDT_ECAPACITY;  // LDS tiers: a run in two registers per lane
   if (b + r < e && w.dact[b + r] == a) {
     if (lane == 0u && w.dctr[b + r] < ctr) w.dctr[b + r] = ctr;
-    ap_sync<C::kG>();
+    sync<C::kG>();
   } else {
     if (c.dot + 1u > C::kDot) return CRDT_ECAPACITY;
     ins_gap<C::kG>(w.dact, c.dot, b + r, 1u, lane);
     ins_gap<C::kG>(w.dctr, c.dot, b + r, 1u, lane);
     if (lane == 0u) { w.dact[b + r] = a; w.dctr[b + r] = ctr; }
-    ap_sync<C::kG>();
+    sync<C::kG>();
     add_range<C::kG>(w.dend, pos, c.mem, 1u, lane);
     c.dot += 1u;
   }
@@ -369,7 +355,7 @@ __device__ int op_add(Ws<C>& w, Cnt& c, bool sparse, uint32_t A, uint32_t a, uin
   } else if (lane == 0u) {
     w.cctr[a] = ctr;
   }
-  ap_sync<C::kG>();
+  sync<C::kG>();
   apply_deferred(w, c, sparse, lane);
   return 0;
 }
@@ -435,11 +421,6 @@ struct ApArgs {
   uint32_t list_cap;
 };
 
-__device__ __forceinline__ uint32_t ap_lane(uint32_t v, uint32_t l) { return __builtin_amdgcn_readlane(v, l); }
-__device__ __forceinline__ uint64_t ap_lane64(uint64_t v, uint32_t l) {
-  return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)(v >> 32), l) << 32) |
-         (uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)v, l);
-}
 // ops q0 .. min(q0 + 64, oe) - 1: lane i holds op q0 + i
 __device__ __forceinline__ void op_fetch(const ApArgs& g, uint64_t q0, uint64_t oe, uint32_t lane, uint32_t& rk,
                                          uint64_t& rm, uint32_t& ra, uint64_t& rn, uint64_t& re) {
@@ -463,10 +444,6 @@ __device__ __forceinline__ void clk_fetch(const ApArgs& g, uint64_t c0, uint64_t
   const uint64_t e = ce < g.n_clk ? ce : g.n_clk;
   if (c0 + lane < e) { xa0 = g.clk_act[c0 + lane]; xc0 = g.clk_ctr[c0 + lane]; }
   if (c0 + kAW + lane < e) { xa1 = g.clk_act[c0 + kAW + lane]; xc1 = g.clk_ctr[c0 + kAW + lane]; }
-}
-__device__ __forceinline__ uint64_t shfl64(uint64_t v, uint32_t j) {
-  return ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(v >> 32), (int)j, kAW) << 32) |
-         (uint64_t)(uint32_t)__shfl((int)(uint32_t)v, (int)j, kAW);
 }
 
 // One object: unpack, run its ops in order, write the canonical record.
@@ -512,7 +489,7 @@ __device__ int apply_one(Ws<C>& w, const ApArgs& g, uint64_t o, uint32_t lane) {
   const uint8_t* r = sb + so;
   Cnt c{};
   if (!rc) {
-    c = Cnt{ap_uni(h[1]), ap_uni(h[2]), ap_uni(h[3]), ap_uni(h[4]), ap_uni(h[5]), ap_uni(h[6]), 0u};
+    c = Cnt{uni32(h[1]), uni32(h[2]), uni32(h[3]), uni32(h[4]), uni32(h[5]), uni32(h[6]), 0u};
     if (c.clk > C::kCk || c.mem > C::kMem || c.dot > C::kDot || c.def > C::kDef || c.fdot > C::kFDot ||
         c.fmem > C::kFMem)
       rc = CRDT_ECAPACITY;
@@ -563,7 +540,7 @@ __device__ int apply_one(Ws<C>& w, const ApArgs& g, uint64_t o, uint32_t lane) {
       w.fdend[i] = ((const uint32_t*)(r + L.o_fdend))[i];
       w.fmend[i] = ((const uint32_t*)(r + L.o_fmend))[i];
     }
-    ap_sync<C::kG>();
+    sync<C::kG>();
     if constexpr (C::kCk <= 2u * kAW) {  // the LDS tiers hold a member's run in two registers per lane
       bool big = false;
       for (uint32_t i = lane; i < c.mem; i += kAW) big = big || w.dend[i] - (i ? w.dend[i - 1] : 0u) > 2u * kAW;
@@ -574,15 +551,15 @@ __device__ int apply_one(Ws<C>& w, const ApArgs& g, uint64_t o, uint32_t lane) {
     const uint32_t qi = (uint32_t)(q - ob) & (kAW - 1u);
     if (qi == 0u && q != ob) {
       op_fetch(g, q, oe, lane, rk, rm, ra, rn, re);
-      pe = ap_uni64(clk_end[q - 1]);
+      pe = uni64(clk_end[q - 1]);
     }
-    const uint32_t k = ap_lane(rk, qi);
-    const uint64_t m = ap_lane64(rm, qi);
+    const uint32_t k = lane32(rk, qi);
+    const uint64_t m = lane64(rm, qi);
     if (k == CRDT_OP_ADD) {
-      rc = op_add(w, c, sparse, A, ap_lane(ra, qi), ap_lane64(rn, qi), m, lane);
-      if (qi == kAW - 1u) pe = ap_lane64(re, qi);
+      rc = op_add(w, c, sparse, A, lane32(ra, qi), lane64(rn, qi), m, lane);
+      if (qi == kAW - 1u) pe = lane64(re, qi);
     } else if (k == CRDT_OP_RM) {
-      const uint64_t b = qi ? ap_lane64(re, qi - 1u) : pe, e = ap_lane64(re, qi);
+      const uint64_t b = qi ? lane64(re, qi - 1u) : pe, e = lane64(re, qi);
       if (qi == kAW - 1u) pe = e;
       if (e < b || e - b > C::kTmp) { rc = e < b ? CRDT_ENONCANON : CRDT_ECAPACITY; break; }
       if (e > g.n_clk) { rc = CRDT_ENONCANON; break; }
@@ -616,7 +593,7 @@ __device__ int apply_one(Ws<C>& w, const ApArgs& g, uint64_t o, uint32_t lane) {
         }
       }
       c.tmp = (uint32_t)(e - b);
-      ap_sync<C::kG>();
+      sync<C::kG>();
       if (__ballot(bad)) { rc = CRDT_ENONCANON; break; }
       rc = op_rm(w, c, sparse, m, lane);
     } else {
@@ -709,19 +686,19 @@ __global__ __launch_bounds__(kAW) void orswot_apply_kernel(ApArgs g, uint8_t* hu
           atomicCAS(g.status, 0, rc);
         }
       }
-      ap_sync<C::kG>();
+      sync<C::kG>();
     }
     return;
   }
   const uint64_t flag = TIER == 1 ? kApPending : kApPendingHuge;
-  const uint32_t n = ap_uni(__hip_atomic_load(&g.ctl[TIER - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+  const uint32_t n = uni32(__hip_atomic_load(&g.ctl[TIER - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
   if (n == 0u) return;
   const bool listed = n <= half;
   const uint64_t* lst = g.list + (TIER == 1 ? 0u : half);
   const uint64_t m = listed ? n : g.n_obj;
   for (uint64_t e = blockIdx.x; e < m; e += gridDim.x) {
-    const uint64_t o = listed ? ap_uni64(lst[e]) : e;
-    if (!listed && !(ap_uni64(g.ooff[o]) & flag)) continue;
+    const uint64_t o = listed ? uni64(lst[e]) : e;
+    if (!listed && !(uni64(g.ooff[o]) & flag)) continue;
     const int rc = apply_one<C>(w, g, o, lane);
     if (rc && lane == 0u) {
       if (TIER == 1 && rc == CRDT_ECAPACITY) {
@@ -732,7 +709,7 @@ __global__ __launch_bounds__(kAW) void orswot_apply_kernel(ApArgs g, uint8_t* hu
         atomicCAS(g.status, 0, rc);
       }
     }
-    ap_sync<C::kG>();
+    sync<C::kG>();
   }
 }
 
@@ -749,8 +726,7 @@ int launch_orswot_apply(const uint8_t* sb, uint64_t sbytes, const uint64_t* soff
                         uint8_t* huge_ws, hipStream_t stream) {
   if (n_obj == 0) return CRDT_OK;
   if (!huge_ws) return CRDT_EINVAL;
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  const int cus = cu_count();
   static std::atomic<int> occ_small{0}, occ_big{0};
   auto occ_of = [](std::atomic<int>& slot, const void* fn) {
     int occ = slot.load(std::memory_order_relaxed);

@@ -26,9 +26,14 @@
 #include "kernels.h"
 #include "sched.h"
 #include "record_layout.h"
+#include "blob.h"
+#include "wave.h"
 
 namespace crdts_hip {
 namespace {
+
+using namespace blob;  // Src, clock_cmp (blob.h)
+using namespace wave;  // sync, uni32 / uni64, lane64, scan_incl (wave.h)
 
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 
@@ -88,99 +93,8 @@ __device__ __forceinline__ void bc_mark(BcStamps* st, int k) {
   }
 }
 
-__device__ __forceinline__ void bc_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// hand-off between the lanes of one wave through the scratch: LDS (the fast
-// path) or HBM (the large-object path, whose stores must have landed)
-template <class XL>
-__device__ __forceinline__ void bc_xsync() {
-  if constexpr (XL::kGlobal) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  } else {
-    bc_sync();
-  }
-}
-
-__device__ __forceinline__ uint32_t bc_uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ uint64_t bc_uni64(uint64_t v) {
-  return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32) |
-         (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v);
-}
-
-__device__ __forceinline__ uint64_t bc_lane64(uint64_t v, uint32_t t) {
-  return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)(v >> 32), t) << 32) |
-         (uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)v, t);
-}
-
-__device__ __forceinline__ uint32_t bc_scan_incl(uint32_t v, uint32_t lane) {
-#pragma unroll
-  for (uint32_t d = 1; d < kBcWave; d <<= 1) {
-    const uint32_t t = __shfl_up(v, d, kBcWave);
-    v += lane >= d ? t : 0u;
-  }
-  return v;
-}
-
-// Blob bytes, read as little-endian unsigned integers of w bytes at a blob
-// position. LDS window (S = true): b is the window's 16-B aligned base and
-// the blob starts at b + d; a field is two aligned u64 reads and a funnel
-// shift (the window has >= 16 spare bytes past the blob). Global (S =
-// false, blobs too large for the window): byte loads.
-template <bool S>
-struct Src;
-template <>
-struct Src<true> {
-  static constexpr bool kWindow = true;
-  const uint8_t* b;
-  uint32_t d;
-  __device__ __forceinline__ uint64_t get(uint64_t pos, uint32_t w) const {
-    const uint32_t a = d + (uint32_t)pos;
-    const uint64_t* q = (const uint64_t*)(b + (a & ~7u));
-    const uint32_t sh = 8u * (a & 7u);
-    const uint64_t lo = q[0], hi = q[1];
-    const uint64_t v = sh ? (lo >> sh) | (hi << (64u - sh)) : lo;
-    return w >= 8u ? v : v & ((1ull << (8u * w)) - 1u);
-  }
-  // the low 32 bits of the field at pos: two aligned u32 reads + v_alignbit
-  __device__ __forceinline__ uint32_t lo32(uint32_t pos) const {
-    const uint32_t a = d + pos;
-    const uint32_t* q = (const uint32_t*)(b + (a & ~3u));
-    return __builtin_amdgcn_alignbit(q[1], q[0], (a & 3u) * 8u);
-  }
-};
-template <>
-struct Src<false> {
-  static constexpr bool kWindow = false;
-  const uint8_t* b;
-  __device__ __forceinline__ uint64_t get(uint64_t pos, uint32_t w) const {
-    uint64_t v = 0;
-    for (uint32_t i = 0; i < w; ++i) v |= (uint64_t)b[pos + i] << (8u * i);
-    return v;
-  }
-};
-__device__ __forceinline__ void wrw(uint8_t* p, uint64_t pos, uint64_t v, uint32_t w) {
-  for (uint32_t i = 0; i < w; ++i) p[pos + i] = (uint8_t)(v >> (8u * i));
-}
-
-// lexicographic (actor, counter) order of two bincode clocks, a proper prefix
-// first (the record's CLOCK ORDER): -1, 0, 1
-template <class SRC>
-__device__ __forceinline__ int bc_clock_cmp(const SRC& B, uint64_t pa, uint32_t na, uint64_t pb, uint32_t nb, uint32_t wa) {
-  const uint32_t n = na < nb ? na : nb, st = wa + 8u;
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint64_t xa = B.get(pa + (uint64_t)st * i, wa), xb = B.get(pb + (uint64_t)st * i, wa);
-    if (xa != xb) return xa < xb ? -1 : 1;
-    const uint64_t ca = B.get(pa + (uint64_t)st * i + wa, 8), cb = B.get(pb + (uint64_t)st * i + wa, 8);
-    if (ca != cb) return ca < cb ? -1 : 1;
-  }
-  return na == nb ? 0 : (na < nb ? -1 : 1);
-}
+// sync<XL::kGlobal>(): the hand-off between the lanes of one wave through the
+// scratch, LDS (the fast path) or HBM (the large-object path)
 
 struct BcWalk {
   uint32_t n_clk, n_mem, n_dot, n_def, n_def_dot, n_def_mem;
@@ -194,11 +108,11 @@ __device__ __forceinline__ BcWalk bc_walk(const SRC& B, uint64_t len, uint32_t w
   BcWalk w{0, 0, 0, 0, 0, 0, 0};
   const uint64_t sa = wa + 8u;
   if (len < 24u || len >= (1ull << 31)) { w.err = CRDT_ENONCANON; return w; }
-  const uint64_t nclk = bc_uni64(B.get(0, 8));
+  const uint64_t nclk = uni64(B.get(0, 8));
   if (nclk > A || nclk * sa > len - 24u) { w.err = CRDT_ENONCANON; return w; }
   w.n_clk = (uint32_t)nclk;
   uint64_t p = 8u + nclk * sa;
-  const uint64_t nent = bc_uni64(B.get(p, 8));
+  const uint64_t nent = uni64(B.get(p, 8));
   p += 8u;
   if (nent > XL::kMem) { w.err = CRDT_ECAPACITY; return w; }
   w.n_mem = (uint32_t)nent;
@@ -208,11 +122,11 @@ __device__ __forceinline__ BcWalk bc_walk(const SRC& B, uint64_t len, uint32_t w
     // byte offset of each entry's length field (clamped into the blob); every
     // length is then validated lane-parallel
     const uint32_t L32 = (uint32_t)len, step = wm + 8u, lim = B.d + L32, sa32 = (uint32_t)sa;
-    uint32_t a = bc_uni(B.d + (uint32_t)p + wm);
+    uint32_t a = uni32(B.d + (uint32_t)p + wm);
     for (uint32_t e0 = 0; e0 < (uint32_t)nent; e0 += kBcWave) {
       // lane j keeps entry e0 + j's length-field offset (a select per step, no stores in the chain)
       uint32_t mine = 0;
-      const uint32_t ne = bc_uni((uint32_t)nent - e0 < kBcWave ? (uint32_t)nent - e0 : kBcWave);
+      const uint32_t ne = uni32((uint32_t)nent - e0 < kBcWave ? (uint32_t)nent - e0 : kBcWave);
       for (uint32_t j = 0; j < ne; ++j) {
         mine = lane == j ? a : mine;
         const uint32_t ac = a < lim ? a : lim;
@@ -223,13 +137,13 @@ __device__ __forceinline__ BcWalk bc_walk(const SRC& B, uint64_t len, uint32_t w
       if (lane < ne) ((uint32_t*)(X + XL::Pm))[e0 + lane] = mine - B.d - wm;
     }
     const uint32_t q = a - B.d - wm;
-    bc_xsync<XL>();
+    sync<XL::kGlobal>();
     for (uint32_t e = lane; e < (uint32_t)nent; e += kBcWave) {  // the full 64-bit lengths, in parallel
       const uint32_t pe = ((const uint32_t*)(X + XL::Pm))[e];
       const uint64_t l = B.get(pe + wm < L32 ? pe + wm : L32, 8);
       ((uint32_t*)(X + XL::Lm))[e] = (l >> 32) ? 0xFFFFFFFFu : (uint32_t)l;
     }
-    bc_xsync<XL>();
+    sync<XL::kGlobal>();
     bool bad = false;
     uint32_t nd = 0;
     for (uint32_t e = lane; e < (uint32_t)nent; e += kBcWave) {
@@ -239,12 +153,12 @@ __device__ __forceinline__ BcWalk bc_walk(const SRC& B, uint64_t len, uint32_t w
     }
     if (__ballot(bad)) { w.err = CRDT_ENONCANON; return w; }
     for (uint32_t dd = 32; dd >= 1; dd >>= 1) nd += __shfl_xor(nd, dd, kBcWave);
-    w.n_dot = bc_uni(nd);
+    w.n_dot = uni32(nd);
     p = q;
   } else {
     for (uint32_t e = 0; e < (uint32_t)nent; ++e) {
       if (p + wm + 8u > len) { w.err = CRDT_ENONCANON; return w; }
-      const uint64_t l = bc_uni64(B.get(p + wm, 8));
+      const uint64_t l = uni64(B.get(p + wm, 8));
       if (l == 0u || l > A || l * sa > len - (p + wm + 8u)) { w.err = CRDT_ENONCANON; return w; }
       if (lane == (e & (kBcWave - 1u))) {
         ((uint32_t*)(X + XL::Pm))[e] = (uint32_t)p;
@@ -255,17 +169,17 @@ __device__ __forceinline__ BcWalk bc_walk(const SRC& B, uint64_t len, uint32_t w
     }
   }
   if (p + 8u > len) { w.err = CRDT_ENONCANON; return w; }
-  const uint64_t ndef = bc_uni64(B.get(p, 8));
+  const uint64_t ndef = uni64(B.get(p, 8));
   p += 8u;
   if (ndef > XL::kDef) { w.err = CRDT_ECAPACITY; return w; }
   w.n_def = (uint32_t)ndef;
   for (uint32_t d = 0; d < (uint32_t)ndef; ++d) {
     if (p + 8u > len) { w.err = CRDT_ENONCANON; return w; }
-    const uint64_t lc = bc_uni64(B.get(p, 8));
+    const uint64_t lc = uni64(B.get(p, 8));
     if (lc == 0u || lc > A || lc * sa > len - (p + 8u)) { w.err = CRDT_ENONCANON; return w; }
     const uint64_t q = p + 8u + lc * sa;
     if (q + 8u > len) { w.err = CRDT_ENONCANON; return w; }
-    const uint64_t ls = bc_uni64(B.get(q, 8));
+    const uint64_t ls = uni64(B.get(q, 8));
     if (ls == 0u || ls > len || ls * wm > len - (q + 8u)) { w.err = CRDT_ENONCANON; return w; }
     if (lane == (d & (kBcWave - 1u))) {
       ((uint32_t*)(X + XL::Pd))[d] = (uint32_t)p;
@@ -287,12 +201,12 @@ template <class XL = XS, class SRC>
 __device__ __forceinline__ void bc_walk_deferred(const SRC& B, uint64_t p, uint32_t wa, uint32_t wm, uint8_t* X,
                                                  uint32_t lane) {
   const uint64_t sa = wa + 8u;
-  const uint32_t ndef = (uint32_t)bc_uni64(B.get(p, 8));
+  const uint32_t ndef = (uint32_t)uni64(B.get(p, 8));
   p += 8u;
   for (uint32_t d = 0; d < ndef; ++d) {
-    const uint64_t lc = bc_uni64(B.get(p, 8));
+    const uint64_t lc = uni64(B.get(p, 8));
     const uint64_t q = p + 8u + lc * sa;
-    const uint64_t ls = bc_uni64(B.get(q, 8));
+    const uint64_t ls = uni64(B.get(q, 8));
     if (lane == (d & (kBcWave - 1u))) {
       ((uint32_t*)(X + XL::Pd))[d] = (uint32_t)p;
       ((uint32_t*)(X + XL::Ld))[d] = (uint32_t)lc;
@@ -315,17 +229,17 @@ __device__ void bc_scan_excl(uint32_t* S, uint32_t n, uint32_t lane) {
       v[k] = i < n ? S[i] : 0u;
       s += v[k];
     }
-    const uint32_t incl = bc_scan_incl(s, lane);
+    const uint32_t incl = scan_incl(s, lane);
     uint32_t run = carry + incl - s;
     carry += __shfl(incl, (int)(kBcWave - 1u), kBcWave);
-    bc_xsync<XL>();
+    sync<XL::kGlobal>();
 #pragma unroll
     for (uint32_t k = 0; k < 4u; ++k) {
       const uint32_t i = b + 4u * lane + k;
       if (i < n) S[i] = run;
       run += v[k];
     }
-    bc_xsync<XL>();
+    sync<XL::kGlobal>();
   }
 }
 
@@ -346,7 +260,7 @@ __device__ __forceinline__ int bc_write_record(const SRC& B, const BcWalk& w, ui
   uint64_t* Kc = (uint64_t*)(X + XL::Kc);
   if (lds_clk) {
     for (uint32_t a = lane; a < A; a += kBcWave) Kc[a] = 0ull;
-    bc_xsync<XL>();
+    sync<XL::kGlobal>();
   } else if (!sparse) {
     for (uint32_t a = lane; a < A; a += kBcWave) ((uint64_t*)(O + L.o_clk))[a] = 0ull;
     __threadfence_block();
@@ -365,7 +279,7 @@ __device__ __forceinline__ int bc_write_record(const SRC& B, const BcWalk& w, ui
     uint64_t px = ((uint64_t)(uint32_t)__shfl_up((int)(uint32_t)(x >> 32), 1, kBcWave) << 32) |
                   (uint32_t)__shfl_up((int)(uint32_t)x, 1, kBcWave);
     if (lane == 0u) px = carry;
-    carry = bc_lane64(x, kBcWave - 1u);
+    carry = lane64(x, kBcWave - 1u);
     if (!on) continue;
     bad = bad || x >= A || c == 0u || (k && px >= x);
     if (x < A) {
@@ -380,9 +294,9 @@ __device__ __forceinline__ int bc_write_record(const SRC& B, const BcWalk& w, ui
     }
   }
   if (lds_clk) {
-    bc_xsync<XL>();
+    sync<XL::kGlobal>();
     for (uint32_t a = lane; a < A; a += kBcWave) ((uint64_t*)(O + L.o_clk))[a] = Kc[a];
-    bc_xsync<XL>();
+    sync<XL::kGlobal>();
   }
   if (sparse && lane == 0u && (w.n_clk & 1u)) *(uint32_t*)(O + L.o_cact + 4u * w.n_clk) = 0u;
   bc_mark<ST>(st, 2);
@@ -391,15 +305,15 @@ __device__ __forceinline__ int bc_write_record(const SRC& B, const BcWalk& w, ui
   uint32_t* Lm = (uint32_t*)(X + XL::Lm) + moff;
   uint32_t* Rm = (uint32_t*)(X + XL::Rm);
   uint32_t* Sm = (uint32_t*)(X + XL::Sm);
-  bc_xsync<XL>();
+  sync<XL::kGlobal>();
   if (w.n_mem <= kBcWave) {  // every key in one register: broadcast by readlane
     const uint64_t k = lane < w.n_mem ? B.get(Pm[lane], wm) : 0ull;
     uint32_t r = 0;
-    for (uint32_t f = 0; f < w.n_mem; ++f) r += bc_lane64(k, f) < k ? 1u : 0u;
+    for (uint32_t f = 0; f < w.n_mem; ++f) r += lane64(k, f) < k ? 1u : 0u;
     // the ranks (# keys below) sum to n (n - 1) / 2 exactly when no two keys are equal
     uint32_t rs = lane < w.n_mem ? r : 0u;
     for (uint32_t dd = 32; dd >= 1; dd >>= 1) rs += __shfl_xor(rs, dd, kBcWave);
-    bad = bad || bc_uni(rs) != w.n_mem * (w.n_mem - 1u) / 2u;
+    bad = bad || uni32(rs) != w.n_mem * (w.n_mem - 1u) / 2u;
     if (lane < w.n_mem) {
       Rm[lane] = r;
       Sm[r < XL::kMem ? r : 0u] = Lm[lane];
@@ -410,7 +324,7 @@ __device__ __forceinline__ int bc_write_record(const SRC& B, const BcWalk& w, ui
     uint64_t* Kk = (uint64_t*)(X + (XL::kGlobal ? XL::Kk : 0u));
     if constexpr (XL::kGlobal) {
       for (uint32_t e = lane; e < w.n_mem; e += kBcWave) Kk[e] = B.get(Pm[e], wm);
-      bc_xsync<XL>();
+      sync<XL::kGlobal>();
     }
     for (uint32_t e = lane; e < w.n_mem; e += kBcWave) {
       const uint64_t k = XL::kGlobal ? Kk[e] : B.get(Pm[e], wm);
@@ -425,7 +339,7 @@ __device__ __forceinline__ int bc_write_record(const SRC& B, const BcWalk& w, ui
       Sm[r < XL::kMem ? r : 0u] = Lm[e];
     }
   }
-  bc_xsync<XL>();
+  sync<XL::kGlobal>();
   bc_scan_excl<XL>(Sm, w.n_mem, lane);
   bc_mark<ST>(st, 3);
   for (uint32_t e = lane; e < w.n_mem; e += kBcWave) {
@@ -456,7 +370,7 @@ __device__ __forceinline__ int bc_write_record(const SRC& B, const BcWalk& w, ui
       uint32_t r = 0;
       for (uint32_t f = 0; f < w.n_def; ++f) {
         if (f == d) continue;
-        const int c = bc_clock_cmp(B, Pd[f] + 8u, Ld[f], Pd[d] + 8u, Ld[d], wa);
+        const int c = clock_cmp(B, Pd[f] + 8u, Ld[f], Pd[d] + 8u, Ld[d], wa);
         r += c < 0 ? 1u : 0u;
         bad = bad || c == 0;  // structurally equal HashMap keys
       }
@@ -464,7 +378,7 @@ __device__ __forceinline__ int bc_write_record(const SRC& B, const BcWalk& w, ui
       Sd[r < XL::kDef ? r : 0u] = Ld[d];
       Ss[r < XL::kDef ? r : 0u] = Ls[d];
     }
-    bc_xsync<XL>();
+    sync<XL::kGlobal>();
     bc_scan_excl<XL>(Sd, w.n_def, lane);
     bc_scan_excl<XL>(Ss, w.n_def, lane);
     for (uint32_t d = lane; d < w.n_def; d += kBcWave) {
@@ -522,7 +436,7 @@ __device__ __forceinline__ int bc_object(const SRC& B, uint64_t o, uint64_t len,
   }
   const uint64_t oo = ooff[o];
   if ((oo & 15u) || oo > out_bytes || size > out_bytes - oo) return CRDT_ECAPACITY;
-  bc_xsync<XL>();
+  sync<XL::kGlobal>();
   return bc_write_record<ST, XL>(B, w, wa, wm, A, sparse, X, out + oo, lane, st);
 }
 
@@ -587,22 +501,22 @@ __global__ __launch_bounds__(kBcWave * kBcWaves, WRITE ? 4 : 5) void bincode_ing
     uint64_t nxt = wins;
     if (nxt) {
       const uint32_t t = (uint32_t)__builtin_ctzll(nxt);
-      bc_prefetch(pf, blobs, blob_bytes, bc_lane64(a0, t), __builtin_amdgcn_readlane(n16, t), lane);
+      bc_prefetch(pf, blobs, blob_bytes, lane64(a0, t), __builtin_amdgcn_readlane(n16, t), lane);
     }
     while (pend) {
       const uint32_t t = (uint32_t)__builtin_ctzll(pend);
       pend &= pend - 1;
-      const uint64_t o = cbase + t, ot = bc_lane64(off, t), lt = bc_lane64(len, t);
+      const uint64_t o = cbase + t, ot = lane64(off, t), lt = lane64(len, t);
       int rc;
       if ((wins >> t) & 1ull) {
-        bc_sync();  // the previous object's window readers are done
+        sync();  // the previous object's window readers are done
 #pragma unroll
         for (uint32_t k = 0; k < kBcPer; ++k) st_s[wave][lane + k * kBcWave] = pf[k];
-        bc_sync();
+        sync();
         nxt &= nxt - 1;  // t was the lowest pending windowed object
         if (nxt) {
           const uint32_t u = (uint32_t)__builtin_ctzll(nxt);
-          bc_prefetch(pf, blobs, blob_bytes, bc_lane64(a0, u), __builtin_amdgcn_readlane(n16, u), lane);
+          bc_prefetch(pf, blobs, blob_bytes, lane64(a0, u), __builtin_amdgcn_readlane(n16, u), lane);
         }
         const Src<true> B{(const uint8_t*)st_s[wave], (uint32_t)(ot & 15u)};
         bc_mark<ST>(st, 0);
@@ -788,13 +702,13 @@ __device__ __forceinline__ int bc_decode_listed(const SRC& B, uint64_t o, uint64
       e = atomicAdd(&ctl[0], 1u);
       if (e < list_cap) list[e] = o;
     }
-    return bc_uni(e) < list_cap ? 0 : CRDT_ECAPACITY;
+    return uni32(e) < list_cap ? 0 : CRDT_ECAPACITY;
   }
   if (w.err) return w.err;
   const uint64_t size = record_size64(sparse ? w.n_clk : A, w.n_mem, w.n_dot, w.n_def, w.n_def_dot, w.n_def_mem,
                                       sparse);
   if (size > out_bytes - oo) return CRDT_ECAPACITY;
-  bc_xsync<XL>();
+  sync<XL::kGlobal>();
   return bc_write_record<false, XL>(B, w, wa, wm, A, sparse, X, out + oo, lane);
 }
 
@@ -884,12 +798,12 @@ __global__ __launch_bounds__(kBcWave * kBcWaves, OCC) void bincode_decode_kernel
       uint64_t rem = wins;
       auto group_of = [&](uint64_t& g, uint64_t& ga, uint32_t& gn) {
         const uint32_t t = (uint32_t)__builtin_ctzll(rem);
-        ga = bc_lane64(a0, t);
+        ga = lane64(a0, t);
         const bool fit = ((rem >> lane) & 1ull) && off >= ga && off + len + 16u <= ga + kBcStage;
         g = __ballot(fit);
         uint32_t e = fit ? (uint32_t)(off + len - ga) : 0u;  // the group's end, < kBcStage past ga
         for (uint32_t dd = 32; dd >= 1; dd >>= 1) e = max(e, (uint32_t)__shfl_xor((int)e, (int)dd, kBcWave));
-        gn = (bc_uni(e) + 15u) / 16u;
+        gn = (uni32(e) + 15u) / 16u;
         rem &= ~g;
       };
       uint64_t gc = 0ull, ga = 0ull;
@@ -903,10 +817,10 @@ __global__ __launch_bounds__(kBcWave * kBcWaves, OCC) void bincode_decode_kernel
       const uint8_t* wb = (const uint8_t*)st_s[wave];
       uint64_t slow = pend & ~wins;  // decoded one by one from HBM after the groups
       while (gc) {
-        bc_sync();  // the previous group's window and scratch readers are done
+        sync();  // the previous group's window and scratch readers are done
 #pragma unroll
         for (uint32_t k = 0; k < kBcPer; ++k) st_s[wave][lane + k * kBcWave] = pf[k];
-        bc_sync();
+        sync();
         const uint64_t gcur = gc, acur = ga;
         gc = 0ull;
         if (rem) {  // the next group's span in flight while this one is decoded
@@ -925,19 +839,19 @@ __global__ __launch_bounds__(kBcWave * kBcWaves, OCC) void bincode_decode_kernel
             cnt = ne <= XS::kMem ? (uint32_t)ne : 0u;
           }
         }
-        const uint32_t incl = bc_scan_incl(cnt, lane), base = incl - cnt;
+        const uint32_t incl = scan_incl(cnt, lane), base = incl - cnt;
         const bool fits = __builtin_amdgcn_readlane(incl, kBcWave - 1u) <= XS::kMem;
         LaneWalk lw2{0, 0, 0, 0, 0, 0, 0, 0};
         if (mine) lw2 = bc_lane_walk_window(Bm, len, wa, wm, A, Pm, Lm, base, fits);
-        bc_xsync<XS>();
+        sync<XS::kGlobal>();
         if (!fits) {  // (entry arrays overflowed: a malformed or oversized group) one object at a time
           slow |= gcur;
           continue;
         }
         for (uint64_t pend2 = gcur; pend2; pend2 &= pend2 - 1) {
           const uint32_t t = (uint32_t)__builtin_ctzll(pend2);
-          const uint64_t o = cbase + t, oot = bc_lane64(oo, t);
-          const Src<true> B{wb, (uint32_t)(bc_lane64(off, t) - acur)};
+          const uint64_t o = cbase + t, oot = lane64(oo, t);
+          const Src<true> B{wb, (uint32_t)(lane64(off, t) - acur)};
           int rc;
           {
             const int err = __builtin_amdgcn_readlane(lw2.err, t);
@@ -947,7 +861,7 @@ __global__ __launch_bounds__(kBcWave * kBcWaves, OCC) void bincode_decode_kernel
                 e = atomicAdd(&ctl[0], 1u);
                 if (e < list_cap) list[e] = o;
               }
-              rc = bc_uni(e) < list_cap ? 0 : CRDT_ECAPACITY;
+              rc = uni32(e) < list_cap ? 0 : CRDT_ECAPACITY;
             } else if (err) {
               rc = err;
             } else {
@@ -964,9 +878,9 @@ __global__ __launch_bounds__(kBcWave * kBcWaves, OCC) void bincode_decode_kernel
               if (size > out_bytes - oot) {
                 rc = CRDT_ECAPACITY;
               } else {
-                bc_sync();  // the previous object's readers of the deferred arrays are done
-                if (w.n_def) bc_walk_deferred(B, bc_lane64(lw2.p_def, t), wa, wm, X, lane);
-                bc_sync();
+                sync();  // the previous object's readers of the deferred arrays are done
+                if (w.n_def) bc_walk_deferred(B, lane64(lw2.p_def, t), wa, wm, X, lane);
+                sync();
                 rc = bc_write_record<false, XL>(B, w, wa, wm, A, sparse, X, out + oot, lane, nullptr,
                                                 __builtin_amdgcn_readlane(base, t));
               }
@@ -978,7 +892,7 @@ __global__ __launch_bounds__(kBcWave * kBcWaves, OCC) void bincode_decode_kernel
       // the blobs past the window (len + 32 > 4 KB): one by one from HBM
       for (uint64_t pend2 = slow; pend2; pend2 &= pend2 - 1) {
         const uint32_t t = (uint32_t)__builtin_ctzll(pend2);
-        const uint64_t o = cbase + t, ot = bc_lane64(off, t), oot = bc_lane64(oo, t), lt = bc_lane64(len, t);
+        const uint64_t o = cbase + t, ot = lane64(off, t), oot = lane64(oo, t), lt = lane64(len, t);
         const Src<false> B{blobs + ot};
         const int rc = bc_decode_listed<XL>(B, o, lt, wa, wm, A, sparse, X, out, oot, out_bytes, ctl, list, list_cap,
                                             lane);
@@ -989,22 +903,22 @@ __global__ __launch_bounds__(kBcWave * kBcWaves, OCC) void bincode_decode_kernel
     uint64_t nxt = wins;
     if (nxt) {
       const uint32_t t = (uint32_t)__builtin_ctzll(nxt);
-      bc_prefetch(pf, blobs, blob_bytes, bc_lane64(a0, t), __builtin_amdgcn_readlane(n16, t), lane);
+      bc_prefetch(pf, blobs, blob_bytes, lane64(a0, t), __builtin_amdgcn_readlane(n16, t), lane);
     }
     while (pend && !LW) {  // read once: walk + decode from the window
       const uint32_t t = (uint32_t)__builtin_ctzll(pend);
       pend &= pend - 1;
-      const uint64_t o = cbase + t, ot = bc_lane64(off, t), oot = bc_lane64(oo, t), lt = bc_lane64(len, t);
+      const uint64_t o = cbase + t, ot = lane64(off, t), oot = lane64(oo, t), lt = lane64(len, t);
       int rc;
       if ((wins >> t) & 1ull) {
-        bc_sync();  // the previous object's window readers are done
+        sync();  // the previous object's window readers are done
 #pragma unroll
         for (uint32_t k = 0; k < kBcPer; ++k) st_s[wave][lane + k * kBcWave] = pf[k];
-        bc_sync();
+        sync();
         nxt &= nxt - 1;  // t was the lowest pending windowed object
         if (nxt) {
           const uint32_t u = (uint32_t)__builtin_ctzll(nxt);
-          bc_prefetch(pf, blobs, blob_bytes, bc_lane64(a0, u), __builtin_amdgcn_readlane(n16, u), lane);
+          bc_prefetch(pf, blobs, blob_bytes, lane64(a0, u), __builtin_amdgcn_readlane(n16, u), lane);
         }
         const Src<true> B{(const uint8_t*)st_s[wave], (uint32_t)(ot & 15u)};
         rc = bc_decode_listed<XL>(B, o, lt, wa, wm, A, sparse, X, out, oot, out_bytes, ctl, list, list_cap, lane);
@@ -1017,7 +931,7 @@ __global__ __launch_bounds__(kBcWave * kBcWaves, OCC) void bincode_decode_kernel
     while (pend && LW) {
       const uint32_t t = (uint32_t)__builtin_ctzll(pend);
       pend &= pend - 1;
-      const uint64_t ot = bc_lane64(off, t), oot = bc_lane64(oo, t);
+      const uint64_t ot = lane64(off, t), oot = lane64(oo, t);
       BcWalk w;
       w.n_clk = __builtin_amdgcn_readlane(lw.n_clk, t);
       w.n_mem = __builtin_amdgcn_readlane(lw.n_mem, t);
@@ -1026,10 +940,10 @@ __global__ __launch_bounds__(kBcWave * kBcWaves, OCC) void bincode_decode_kernel
       w.n_def_dot = __builtin_amdgcn_readlane(lw.n_fdot, t);
       w.n_def_mem = __builtin_amdgcn_readlane(lw.n_fmem, t);
       w.err = 0;
-      const uint64_t pdef = bc_lane64(lw.p_def, t);
+      const uint64_t pdef = lane64(lw.p_def, t);
       // the parked (position, dot count) pairs -> the walk's LDS arrays
       const uint64_t* keyarea = (const uint64_t*)(out + oot + kHdrBytes + clock_bytes(sparse ? w.n_clk : A, sparse));
-      bc_sync();
+      sync();
       for (uint32_t e = lane; e < w.n_mem; e += kBcWave) {
         const uint64_t pr = keyarea[e];
         ((uint32_t*)(X + XS::Pm))[e] = (uint32_t)pr;
@@ -1039,20 +953,20 @@ __global__ __launch_bounds__(kBcWave * kBcWaves, OCC) void bincode_decode_kernel
       if ((wins >> t) & 1ull) {
 #pragma unroll
         for (uint32_t k = 0; k < kBcPer; ++k) st_s[wave][lane + k * kBcWave] = pf[k];
-        bc_sync();
+        sync();
         nxt &= nxt - 1;  // t was the lowest pending windowed object
         if (nxt) {
           const uint32_t u = (uint32_t)__builtin_ctzll(nxt);
-          bc_prefetch(pf, blobs, blob_bytes, bc_lane64(a0, u), __builtin_amdgcn_readlane(n16, u), lane);
+          bc_prefetch(pf, blobs, blob_bytes, lane64(a0, u), __builtin_amdgcn_readlane(n16, u), lane);
         }
         const Src<true> B{(const uint8_t*)st_s[wave], (uint32_t)(ot & 15u)};
         if (w.n_def) bc_walk_deferred(B, pdef, wa, wm, X, lane);
-        bc_sync();
+        sync();
         rc = bc_write_record(B, w, wa, wm, A, sparse, X, out + oot, lane);
       } else {
         const Src<false> B{blobs + ot};
         if (w.n_def) bc_walk_deferred(B, pdef, wa, wm, X, lane);
-        bc_sync();
+        sync();
         rc = bc_write_record(B, w, wa, wm, A, sparse, X, out + oot, lane);
       }
       if (rc && lane == 0u) atomicCAS(status, 0, rc);
@@ -1071,10 +985,10 @@ __global__ __launch_bounds__(kBcWave) void bincode_decode_big_kernel(
   const uint32_t lane = threadIdx.x;
   uint8_t* X = scratch + (uint64_t)blockIdx.x * XB::Bytes;
   const bool sparse = (flags & kSparseClock) != 0u;
-  const uint32_t n = bc_uni(__hip_atomic_load(&ctl[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+  const uint32_t n = uni32(__hip_atomic_load(&ctl[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
   const uint32_t m = n < list_cap ? n : list_cap;
   for (uint32_t e = blockIdx.x; e < m; e += gridDim.x) {
-    const uint64_t o = bc_uni64(list[e]);
+    const uint64_t o = uni64(list[e]);
     const Src<false> B{blobs + boff[o]};
     const int rc = bc_object<true, false, XB>(B, o, blen[o], wa, wm, A, sparse, X, nullptr, out, ooff, out_bytes, lane);
     if (rc && lane == 0u) atomicCAS(status, 0, rc);
@@ -1124,12 +1038,12 @@ __device__ __forceinline__ uint64_t bc_blob_len(const uint32_t* h, uint32_t wa, 
 // nonzero top-clock entries of a record (dense: count of nonzero slots)
 __device__ __forceinline__ uint32_t bc_nnz(const uint8_t* r, uint32_t lane) {
   const uint32_t* h = (const uint32_t*)r;
-  if (h[7] & kSparseClock) return bc_uni(h[1]);
-  const uint32_t n_clk = bc_uni(h[1]);
+  if (h[7] & kSparseClock) return uni32(h[1]);
+  const uint32_t n_clk = uni32(h[1]);
   uint32_t n = 0;
   for (uint32_t a = lane; a < n_clk; a += kBcWave) n += ((const uint64_t*)(r + kHdrBytes))[a] != 0u ? 1u : 0u;
   for (uint32_t d = 32; d >= 1; d >>= 1) n += __shfl_xor(n, d, kBcWave);
-  return bc_uni(n);
+  return uni32(n);
 }
 
 __device__ bool bc_record_ok(const uint8_t* base, uint64_t bytes, uint64_t off, uint32_t A, uint32_t flags) {
@@ -1147,10 +1061,10 @@ template <class DST>
 __device__ __forceinline__ bool bc_emit(const uint8_t* r, const DST& T, uint32_t nnz, uint32_t wa, uint32_t wm,
                                         uint64_t amax, uint64_t mmax, uint32_t lane) {
   const uint32_t* h = (const uint32_t*)r;
-  const uint32_t n_clk = bc_uni(h[1]), n_mem = bc_uni(h[2]), n_dot = bc_uni(h[3]), n_def = bc_uni(h[4]);
-  const bool sparse = (bc_uni(h[7]) & kSparseClock) != 0u;
+  const uint32_t n_clk = uni32(h[1]), n_mem = uni32(h[2]), n_dot = uni32(h[3]), n_def = uni32(h[4]);
+  const bool sparse = (uni32(h[7]) & kSparseClock) != 0u;
   RecLayout L;
-  rec_layout(L, n_clk, n_mem, n_dot, n_def, bc_uni(h[5]), bc_uni(h[6]), sparse);
+  rec_layout(L, n_clk, n_mem, n_dot, n_def, uni32(h[5]), uni32(h[6]), sparse);
   const uint64_t sa = wa + 8u;
   bool bad = false;
   // top clock: BTreeMap<A, u64> = length, then (actor, counter) ascending
@@ -1252,7 +1166,7 @@ __global__ __launch_bounds__(kBcWave * kBcWaves, WRITE ? 4 : 8) void bincode_ege
       while (pend) {
         const uint32_t t = (uint32_t)__builtin_ctzll(pend);
         pend &= pend - 1;
-        const uint8_t* r = rb + bc_lane64(ro, t);
+        const uint8_t* r = rb + lane64(ro, t);
         const uint32_t nnz = bc_nnz(r, lane);
         if (lane == 0u) sizes[cbase + t] = bc_blob_len((const uint32_t*)r, wa, wm, nnz);
       }
@@ -1264,7 +1178,7 @@ __global__ __launch_bounds__(kBcWave * kBcWaves, WRITE ? 4 : 8) void bincode_ege
     uint64_t nxt = wins;
     if (nxt) {
       const uint32_t t = (uint32_t)__builtin_ctzll(nxt);
-      bc_prefetch(pf, rb, rbytes, bc_lane64(ro, t), __builtin_amdgcn_readlane(rsz, t) / 16u, lane);
+      bc_prefetch(pf, rb, rbytes, lane64(ro, t), __builtin_amdgcn_readlane(rsz, t) / 16u, lane);
     }
     bool bad = (uint64_t)(A - 1u) > amax;
     while (pend) {
@@ -1272,14 +1186,14 @@ __global__ __launch_bounds__(kBcWave * kBcWaves, WRITE ? 4 : 8) void bincode_ege
       pend &= pend - 1;
       const uint64_t o = cbase + t, oo = ooff[o];
       if ((wins >> t) & 1ull) {
-        bc_sync();  // the previous object's window readers are done
+        sync();  // the previous object's window readers are done
 #pragma unroll
         for (uint32_t k = 0; k < kBcPer; ++k) rs_s[wave][lane + k * kBcWave] = pf[k];
-        bc_sync();
+        sync();
         nxt &= nxt - 1;
         if (nxt) {
           const uint32_t u = (uint32_t)__builtin_ctzll(nxt);
-          bc_prefetch(pf, rb, rbytes, bc_lane64(ro, u), __builtin_amdgcn_readlane(rsz, u) / 16u, lane);
+          bc_prefetch(pf, rb, rbytes, lane64(ro, u), __builtin_amdgcn_readlane(rsz, u) / 16u, lane);
         }
         const uint8_t* r = (const uint8_t*)rs_s[wave];
         const uint32_t nnz = bc_nnz(r, lane);
@@ -1290,9 +1204,9 @@ __global__ __launch_bounds__(kBcWave * kBcWaves, WRITE ? 4 : 8) void bincode_ege
         }
         if (padded <= kBcStage) {
           for (uint32_t k = lane; k < (uint32_t)(padded / 16u); k += kBcWave) ts_s[wave][k] = v4u{0u, 0u, 0u, 0u};
-          bc_sync();
+          sync();
           bad = bc_emit(r, Dst<true>{(uint8_t*)ts_s[wave]}, nnz, wa, wm, amax, mmax, lane) || bad;
-          bc_sync();
+          sync();
           for (uint32_t k = lane; k < (uint32_t)(padded / 16u); k += kBcWave)
             __builtin_nontemporal_store(ts_s[wave][k], (v4u*)(out + oo) + k);
         } else {
@@ -1300,7 +1214,7 @@ __global__ __launch_bounds__(kBcWave * kBcWaves, WRITE ? 4 : 8) void bincode_ege
           bad = bc_emit(r, Dst<false>{out + oo}, nnz, wa, wm, amax, mmax, lane) || bad;
         }
       } else {
-        const uint8_t* r = rb + bc_lane64(ro, t);
+        const uint8_t* r = rb + lane64(ro, t);
         const uint32_t nnz = bc_nnz(r, lane);
         const uint64_t len = bc_blob_len((const uint32_t*)r, wa, wm, nnz), padded = (len + 15u) & ~15ull;
         if ((oo & 15u) || oo > out_bytes || padded > out_bytes - oo) {
@@ -1318,8 +1232,7 @@ __global__ __launch_bounds__(kBcWave * kBcWaves, WRITE ? 4 : 8) void bincode_ege
 // A resident grid for the guided split (every wave's static chunks start at
 // once): the kernel's occupancy in blocks per CU, cached per kernel.
 uint32_t bc_resident_blocks(uint64_t n_obj, const void* fn, std::atomic<int>& occ_cache) {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  const int cus = cu_count();
   int occ = occ_cache.load(std::memory_order_relaxed);
   if (occ == 0) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, kBcWave * kBcWaves, 0) != hipSuccess || occ < 1)
@@ -1331,10 +1244,7 @@ uint32_t bc_resident_blocks(uint64_t n_obj, const void* fn, std::atomic<int>& oc
 }
 
 uint32_t bc_blocks(uint64_t n_obj) {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const uint64_t want = (n_obj + kBcWaves - 1) / kBcWaves, cap = (uint64_t)cus * 8u;
-  return (uint32_t)(want < cap ? want : cap);
+  return resident_blocks((n_obj + kBcWaves - 1) / kBcWaves);
 }
 
 // Record placement without reading the blobs: a bound on the record size of
@@ -1388,11 +1298,7 @@ int launch_bincode_ingest(const uint8_t* blobs, uint64_t blob_bytes, const uint6
     return hipGetLastError() == hipSuccess ? CRDT_OK : CRDT_EHIP;
   }
   if (sizes) {  // one lane per blob
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess)
-      (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const uint64_t want = (n_obj + 255u) / 256u, cap = (uint64_t)cus * 8u;
-    hipLaunchKernelGGL(bincode_sizes_lane_kernel, dim3((uint32_t)(want < cap ? want : cap)), dim3(256), 0, stream,
+    hipLaunchKernelGGL(bincode_sizes_lane_kernel, dim3(resident_blocks((n_obj + 255u) / 256u)), dim3(256), 0, stream,
                        blobs, blob_bytes, boff, blen, n_obj, wa, wm, A, flags, sizes, status);
   } else {
     if (hipMemsetAsync(ctl, 0, 4 * sizeof(uint32_t), stream) != hipSuccess) return CRDT_EHIP;  // ctl[3]: tickets

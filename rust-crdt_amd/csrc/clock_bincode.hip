@@ -32,40 +32,25 @@
 #include "csr_rank.h"
 #include "ctx.h"
 #include "kernels.h"
+#include "sched.h"
 
 namespace crdts_hip {
 namespace {
 
 using namespace csr_rank;
 
-constexpr uint32_t kW = 64;
 constexpr uint32_t kBlock = 256;
 constexpr uint32_t kTile = 1024;  // u64 words of LDS per wave (dense ingest)
 
-__device__ __forceinline__ void fail(int* status, int code) { atomicCAS(status, 0, code); }
-
-// LDS stores of this wave's lanes are visible to its other lanes
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-uint32_t resident_blocks(uint64_t want) {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const uint64_t cap = (uint64_t)cus * 8;  // 8 blocks of 4 waves per CU
-  return (uint32_t)(want < cap ? want : cap);
-}
 
 // ------------------------------------------------------------- byte fields
 // [lo, hi): the bytes that may be read (d_blobs)
-struct Src {
+struct Bounds {
   uintptr_t lo, hi;
 };
 
 template <uint32_t W>
-__device__ __forceinline__ uint64_t rd_le(const uint8_t* p, const Src& s) {
+__device__ __forceinline__ uint64_t rd_le(const uint8_t* p, const Bounds& s) {
   const uint32_t r = (uint32_t)((uintptr_t)p & 7u);
   const uintptr_t w0 = (uintptr_t)p - r;
   const bool two = r + W > 8u;
@@ -136,7 +121,7 @@ struct Frame {
 
 template <uint32_t AB>
 __device__ __forceinline__ Frame frame(const uint8_t* blobs, uint64_t blob_bytes, uint64_t off, uint64_t len,
-                                       uint32_t nc, uint64_t n_max, const Src& src) {
+                                       uint32_t nc, uint64_t n_max, const Bounds& src) {
   constexpr uint64_t E = AB + 8u;
   Frame F{};
   F.ok = off <= blob_bytes && len <= blob_bytes - off;
@@ -193,7 +178,7 @@ __device__ __forceinline__ uint64_t owners(bool bad, uint32_t t) {
   while (m) {
     const uint32_t l = (uint32_t)__builtin_ctzll(m);
     m &= m - 1u;
-    r |= 1ull << lane_u32(t, l);
+    r |= 1ull << lane32(t, l);
   }
   return r;
 }
@@ -205,7 +190,7 @@ __device__ __forceinline__ uint64_t owners(bool bad, uint32_t t) {
 // calls f(t, k, actor, counter, live) (f may read across lanes); `live` says
 // the lane holds a good entry.
 template <uint32_t AB, class F>
-__device__ __forceinline__ uint64_t walk_blobs(const uint8_t* blobs, const Src& src, uint64_t n, uint64_t pos,
+__device__ __forceinline__ uint64_t walk_blobs(const uint8_t* blobs, const Bounds& src, uint64_t n, uint64_t pos,
                                                uint64_t limit, uint32_t lane, F f) {
   constexpr uint64_t E = AB + 8u;
   uint64_t badobj = 0;
@@ -237,7 +222,7 @@ __global__ __launch_bounds__(kBlock) void dense_from_kernel(const uint8_t* blobs
   const uint32_t lane = threadIdx.x & (kW - 1u);
   const uint64_t wave = (uint64_t)blockIdx.x * (kBlock / kW) + threadIdx.x / kW;
   const uint64_t n_waves = (uint64_t)gridDim.x * (kBlock / kW);
-  const Src src{(uintptr_t)blobs, (uintptr_t)blobs + blob_bytes};
+  const Bounds src{(uintptr_t)blobs, (uintptr_t)blobs + blob_bytes};
   const uint64_t S = (uint64_t)A * nc;
   const bool windows = S > kTile;              // then R == 1
   const uint64_t rowW = windows ? kTile : S;   // a row's words in the tile
@@ -264,7 +249,7 @@ __global__ __launch_bounds__(kBlock) void dense_from_kernel(const uint8_t* blobs
     for (uint64_t w0 = 0; w0 < S; w0 += kTile) {
       const uint64_t words = windows ? (S - w0 < kTile ? S - w0 : kTile) : live * S;
       for (uint64_t k = lane; k < words; k += kW) tile[k] = 0ull;
-      wave_sync();
+      sync();
       uint64_t bo = 0;
 #pragma unroll
       for (uint32_t c = 0; c < 2u; ++c) {
@@ -278,7 +263,7 @@ __global__ __launch_bounds__(kBlock) void dense_from_kernel(const uint8_t* blobs
       mybad = mybad || ((bo >> lane) & 1u);
       uint64_t zero = __ballot(mybad);  // a bad object's row is all zero
       if (zero) {
-        wave_sync();
+        sync();
         if (lane == 0u) fail(status, CRDT_ENONCANON);
         while (zero) {
           const uint32_t t = (uint32_t)__builtin_ctzll(zero);
@@ -286,10 +271,10 @@ __global__ __launch_bounds__(kBlock) void dense_from_kernel(const uint8_t* blobs
           for (uint64_t k = lane; k < (windows ? words : S); k += kW) tile[t * rowW + k] = 0ull;
         }
       }
-      wave_sync();
+      sync();
       uint64_t* dst = rows + c0 * S + w0;
       for (uint64_t k = lane; k < words; k += kW) dst[k] = tile[k];
-      wave_sync();  // the tile is free again
+      sync();  // the tile is free again
     }
   }
 }
@@ -382,7 +367,7 @@ template <uint32_t AB>
 __global__ __launch_bounds__(kBlock) void csr_lens_kernel(const uint8_t* blobs, uint64_t blob_bytes,
                                                           const uint64_t* boff, const uint64_t* blen, uint64_t n_obj,
                                                           uint32_t nc, uint32_t* len_p, uint32_t* len_n, int* status) {
-  const Src src{(uintptr_t)blobs, (uintptr_t)blobs + blob_bytes};
+  const Bounds src{(uintptr_t)blobs, (uintptr_t)blobs + blob_bytes};
   for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n_obj; i += (uint64_t)gridDim.x * kBlock) {
     const Frame F = frame<AB>(blobs, blob_bytes, boff[i], blen[i], nc, 0xffffffffull, src);
     if (!F.ok) fail(status, CRDT_ENONCANON);
@@ -399,7 +384,7 @@ __global__ __launch_bounds__(kBlock) void csr_from_kernel(const uint8_t* blobs, 
   const uint32_t lane = threadIdx.x & (kW - 1u);
   const uint64_t wave = (uint64_t)blockIdx.x * (kBlock / kW) + threadIdx.x / kW;
   const uint64_t n_waves = (uint64_t)gridDim.x * (kBlock / kW);
-  const Src src{(uintptr_t)blobs, (uintptr_t)blobs + blob_bytes};
+  const Bounds src{(uintptr_t)blobs, (uintptr_t)blobs + blob_bytes};
   for (uint64_t ch = wave; ch < chunks; ch += n_waves) {
     const uint64_t i = ch * kW + lane;
     const bool valid = i < n_obj;
@@ -530,7 +515,7 @@ __global__ __launch_bounds__(kBlock) void ops_from_kernel(const uint8_t* blobs, 
                                                           uint32_t* actor, uint64_t* counter, uint32_t* dir,
                                                           int* status) {
   constexpr uint64_t size = AB + 8u + (DIR ? 4u : 0u);
-  const Src src{(uintptr_t)blobs, (uintptr_t)blobs + (n - 1u) * stride + size};
+  const Bounds src{(uintptr_t)blobs, (uintptr_t)blobs + (n - 1u) * stride + size};
   for (uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x; j < n; j += (uint64_t)gridDim.x * kBlock) {
     const uint8_t* p = blobs + j * stride;
     uint64_t a = rd_le<AB>(p, src), c = rd_le<8>(p + AB, src);

@@ -39,6 +39,7 @@
 #include "../../include/crdts_hip.h"
 #include "csr_rank.h"
 #include "kernels.h"
+#include "sched.h"
 
 namespace crdts_hip {
 namespace {
@@ -47,25 +48,9 @@ using namespace csr_rank;
 
 typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
 
-constexpr uint32_t kW = 64;
 constexpr uint32_t kBlock = 256;
 constexpr int kUnroll = 4;
 
-__device__ __forceinline__ void fail(int* status, int code) { atomicCAS(status, 0, code); }
-
-// stores of this wave's lanes are visible to its other lanes
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-uint32_t resident_blocks(uint64_t want) {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const uint64_t cap = (uint64_t)cus * 8;  // 8 blocks of 4 waves per CU
-  return (uint32_t)(want < cap ? want : cap);
-}
 
 // ---------------------------------------------------------------- dense binops
 template <int OP>
@@ -389,8 +374,8 @@ __global__ __launch_bounds__(kBlock) void csr_filter_kernel(CsrIn S, CsrIn O, Cs
     while (pend) {  // the chunk's objects one by one, the whole wave on each
       const uint32_t t = (uint32_t)__builtin_ctzll(pend);
       pend &= pend - 1u;
-      const uint64_t s0 = lane_u64(so, t);
-      uint32_t U = filter_one<OP>(S, O, R, s0, lane_u32(sl, t), lane_u64(oo, t), lane_u32(ol, t), s0, lane);
+      const uint64_t s0 = lane64(so, t);
+      uint32_t U = filter_one<OP>(S, O, R, s0, lane32(sl, t), lane64(oo, t), lane32(ol, t), s0, lane);
       if (U == ~0u) {
         U = 0u;
         noncanon = true;
@@ -481,15 +466,15 @@ __device__ uint32_t canon_long(const ApplyJob& J, uint64_t bb, uint32_t m, uint3
       const uint64_t yl = kl < m ? ya[kl] : 0ull;
       const uint32_t cnt = m - kb < kW ? m - kb : kW;
       for (uint32_t kk = 0; kk < cnt; ++kk) {
-        const uint32_t xk = lane_u32(xl, kk);
-        const uint64_t yk = lane_u64(yl, kk);
+        const uint32_t xk = lane32(xl, kk);
+        const uint64_t yk = lane64(yl, kk);
         if (yk && xk == x && (yk > y || (yk == y && kb + kk < j))) rep = false;
       }
     }
     if (h) J.w_flag[bb + j] = rep ? 1u : 0u;
     mo += (uint32_t)__popcll(__ballot(rep));
   }
-  wave_sync();
+  sync();
   for (uint32_t base = 0; base < m; base += kW) {
     const uint32_t j = base + lane;
     const bool h = j < m;
@@ -504,7 +489,7 @@ __device__ uint32_t canon_long(const ApplyJob& J, uint64_t bb, uint32_t m, uint3
       while (F) {
         const uint32_t kk = (uint32_t)__builtin_ctzll(F);
         F &= F - 1u;
-        rnk += lane_u32(xl, kk) < x ? 1u : 0u;
+        rnk += lane32(xl, kk) < x ? 1u : 0u;
       }
     }
     if (rep) {
@@ -512,7 +497,7 @@ __device__ uint32_t canon_long(const ApplyJob& J, uint64_t bb, uint32_t m, uint3
       J.w_ctr[bb + rnk] = y;
     }
   }
-  wave_sync();
+  sync();
   return mo;
 }
 
@@ -533,14 +518,14 @@ __device__ __forceinline__ uint32_t apply_one(const ApplyJob& J, uint64_t s0, ui
     const uint64_t y = hq ? J.counter[bb + lane] : 0ull;
     bool rep = hq && y > 0ull;
     for (uint32_t k = 0; k < m; ++k) {
-      const uint32_t xk = lane_u32(x, k);
-      const uint64_t yk = lane_u64(y, k);
+      const uint32_t xk = lane32(x, k);
+      const uint64_t yk = lane64(y, k);
       if (yk && xk == x && (yk > y || (yk == y && k < lane))) rep = false;
     }
     const uint64_t Rm = __ballot(rep);
     mo = (uint32_t)__popcll(Rm);
     uint32_t rnk = 0;
-    for (uint64_t F = Rm; F; F &= F - 1u) rnk += lane_u32(x, (uint32_t)__builtin_ctzll(F)) < x ? 1u : 0u;
+    for (uint64_t F = Rm; F; F &= F - 1u) rnk += lane32(x, (uint32_t)__builtin_ctzll(F)) < x ? 1u : 0u;
     // lane p <- the standing dot of rank p (the others push to lane 63, which
     // is past the run whenever one of them exists)
     const int dst = (int)((rep ? rnk : 63u) << 2);
@@ -578,7 +563,7 @@ __device__ __forceinline__ uint32_t apply_one(const ApplyJob& J, uint64_t s0, ui
       J.w_act[bb + lane] = b;
       J.w_ctr[bb + lane] = d;
     }
-    wave_sync();
+    sync();
   } else {
     if (m64 > 0xfffffffeull - ns) return ~0u;  // (a u32 length cannot hold it)
     mo = canon_long(J, bb, (uint32_t)m64, lane);
@@ -613,8 +598,8 @@ __global__ __launch_bounds__(kBlock) void csr_apply_kernel(ApplyJob J, uint64_t 
     while (pend) {
       const uint32_t t = (uint32_t)__builtin_ctzll(pend);
       pend &= pend - 1u;
-      const uint64_t s0 = lane_u64(so, t), bb = lane_u64(b, t), ee = lane_u64(e, t);
-      uint32_t U = apply_one(J, s0, lane_u32(sl, t), bb, ee - bb, s0 + bb, lane);
+      const uint64_t s0 = lane64(so, t), bb = lane64(b, t), ee = lane64(e, t);
+      uint32_t U = apply_one(J, s0, lane32(sl, t), bb, ee - bb, s0 + bb, lane);
       if (U == ~0u) {
         U = 0u;
         noncanon = true;
@@ -651,8 +636,8 @@ __global__ __launch_bounds__(kBlock) void csr_value_kernel(CsrIn S, uint64_t* ou
     while (pend) {
       const uint32_t t = (uint32_t)__builtin_ctzll(pend);
       pend &= pend - 1u;
-      const uint64_t s0 = lane_u64(so, t);
-      const uint32_t ns = lane_u32(sl, t);
+      const uint64_t s0 = lane64(so, t);
+      const uint32_t ns = lane32(sl, t);
       uint64_t v = 0;
       for (uint32_t k = lane; k < ns; k += kW) v += S.ctr[s0 + k];
       v = group_sum<64>(v, lane);

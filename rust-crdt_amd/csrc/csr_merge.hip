@@ -30,11 +30,11 @@
 #include "../../include/crdts_hip.h"
 #include "csr_rank.h"
 #include "kernels.h"
+#include "sched.h"
 
 namespace crdts_hip {
 namespace {
 
-constexpr uint32_t kW = 64;
 constexpr uint32_t kBlock = 256;
 
 struct CsrJob {
@@ -56,9 +56,7 @@ struct CsrJob {
   uint64_t n;
 };
 
-using namespace csr_rank;  // rd32 / rd64 / lane_u32 / lane_u64 / mbcnt / from_below / rank_regs / rank_mem
-
-__device__ __forceinline__ void fail(int* status, int code) { atomicCAS(status, 0, code); }
+using namespace csr_rank;  // rd32 / rd64 / from_below / rank_regs / rank_mem, and the wave toolkit (wave.h)
 
 // Runs longer than 64 entries: 64-entry chunks of each side, each entry's
 // rank in the other run by binary search in HBM. Returns the union length,
@@ -146,23 +144,23 @@ __device__ __forceinline__ void merge_chunk(const CsrJob& J, uint64_t c0, uint32
     uint32_t pa = 0u, qa = 0u;
     uint64_t pc = 1ull, qc = 1ull;
     if (pend) {
-      const uint32_t ns = lane_u32(sl, t), no = lane_u32(ol, t);
-      const uint64_t s0 = lane_u64(so, t), o0 = lane_u64(oo, t);
+      const uint32_t ns = lane32(sl, t), no = lane32(ol, t);
+      const uint64_t s0 = lane64(so, t), o0 = lane64(oo, t);
       if (lane < ns && ns <= kW) { pa = J.sa[s0 + lane]; pc = J.sc[s0 + lane]; }
       if (lane < no && no <= kW) { qa = J.oa[o0 + lane]; qc = J.oc[o0 + lane]; }
     }
     while (pend) {
       t = (uint32_t)__builtin_ctzll(pend);
       pend &= pend - 1u;
-      const uint32_t ns = lane_u32(sl, t), no = lane_u32(ol, t);
-      const uint64_t s0 = lane_u64(so, t), o0 = lane_u64(oo, t);
+      const uint32_t ns = lane32(sl, t), no = lane32(ol, t);
+      const uint64_t s0 = lane64(so, t), o0 = lane64(oo, t);
       const uint64_t ob = s0 + o0;
       const uint32_t a = pa, b = qa;
       const uint64_t c = pc, d = qc;
       if (pend) {  // the next object's runs
         const uint32_t u = (uint32_t)__builtin_ctzll(pend);
-        const uint32_t nsu = lane_u32(sl, u), nou = lane_u32(ol, u);
-        const uint64_t su = lane_u64(so, u), ou = lane_u64(oo, u);
+        const uint32_t nsu = lane32(sl, u), nou = lane32(ol, u);
+        const uint64_t su = lane64(so, u), ou = lane64(oo, u);
         pa = 0u; qa = 0u; pc = 1ull; qc = 1ull;
         if (lane < nsu && nsu <= kW) { pa = J.sa[su + lane]; pc = J.sc[su + lane]; }
         if (lane < nou && nou <= kW) { qa = J.oa[ou + lane]; qc = J.oc[ou + lane]; }
@@ -224,8 +222,7 @@ __global__ __launch_bounds__(kBlock) void clock_csr_merge_kernel(CsrJob J, uint6
 
 int launch_clock_csr_merge(const crdt_clock_csr* const* self, const crdt_clock_csr* const* other,
                            const crdt_clock_csr_out* const* out, int n_jobs, int* status, hipStream_t stream) {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  const int cus = cu_count();
   for (int k = 0; k < n_jobs; ++k) {  // PNCounter: P, then N (independent joins, one stream)
     const CsrJob J{self[k]->off, self[k]->len, self[k]->act, self[k]->ctr, self[k]->n_entries,
                    other[k]->off, other[k]->len, other[k]->act, other[k]->ctr, other[k]->n_entries,

@@ -1,27 +1,25 @@
-// Wave-level helpers of the CSR clock kernels (csr_merge.hip, clock_ops.hip):
-// cross-lane reads, the ballot prefix count, and the rank of an actor in a
-// sorted run held in registers (<= 64 entries, one per lane) or in HBM.
+// Wave-level helpers of the CSR clock kernels (csr_merge.hip, clock_ops.hip,
+// read.hip, lwwreg.hip, clock_bincode.hip): the ds_bpermute cross-lane reads,
+// the rank of an actor in a sorted run held in registers (<= 64 entries, one
+// per lane) or in HBM, and the flat walk over the op ranges of 64 objects. The
+// readlane reads (lane32 / lane64), the ballot prefix count (mbcnt) and fail
+// are wave.h's, seen through namespace csr_rank.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "wave.h"
+
 namespace crdts_hip {
 namespace csr_rank {
+
+using namespace wave;
 
 __device__ __forceinline__ uint32_t rd32(uint32_t v, uint32_t src) {
   return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(src << 2), (int)v);
 }
 __device__ __forceinline__ uint64_t rd64(uint64_t v, uint32_t src) {
   return ((uint64_t)rd32((uint32_t)(v >> 32), src) << 32) | rd32((uint32_t)v, src);
-}
-__device__ __forceinline__ uint32_t lane_u32(uint32_t v, uint32_t l) {
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l);
-}
-__device__ __forceinline__ uint64_t lane_u64(uint64_t v, uint32_t l) {
-  return ((uint64_t)lane_u32((uint32_t)(v >> 32), l) << 32) | lane_u32((uint32_t)v, l);
-}
-__device__ __forceinline__ uint32_t mbcnt(uint64_t m) {
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 // lane k's value moved to lane k + 1 (lane 0 gets 0): DPP wave_shr:1
 __device__ __forceinline__ uint32_t from_below(uint32_t v) {
@@ -54,7 +52,7 @@ __device__ __forceinline__ void for_each_in_ranges(bool valid, bool good, uint64
                                                    F f) {
   const uint64_t badm = __ballot(valid && !good);
   const uint32_t nv = (uint32_t)__popcll(__ballot(valid));  // the valid lanes are [0, nv), nv >= 1
-  const uint64_t start = lane_u64(b, 0u), span = lane_u64(e, nv - 1u) - start;
+  const uint64_t start = lane64(b, 0u), span = lane64(e, nv - 1u) - start;
   if (!badm && span < 0xffffffffull) {
     // the ends ascend: op j belongs to the object after the last end <= j
     const uint32_t T = (uint32_t)span;
@@ -70,7 +68,7 @@ __device__ __forceinline__ void for_each_in_ranges(bool valid, bool good, uint64
     while (run) {
       const uint32_t t = (uint32_t)__builtin_ctzll(run);
       run &= run - 1u;
-      const uint64_t bb = lane_u64(b, t), ee = lane_u64(e, t);
+      const uint64_t bb = lane64(b, t), ee = lane64(e, t);
       for (uint64_t j0 = bb; j0 < ee; j0 += 64u) f(j0 + lane, j0 + lane < ee, t);
     }
   }

@@ -12,6 +12,7 @@
 
 #include "../../include/crdts_hip.h"
 #include "kernels.h"
+#include "sched.h"
 
 namespace crdts_hip {
 namespace {
@@ -62,12 +63,8 @@ int launch_dense_max(uint64_t* self, const uint64_t* other, uint64_t n_words, hi
   const bool aligned = ((uintptr_t)self % 16 == 0) && ((uintptr_t)other % 16 == 0);
   uint64_t n2 = aligned ? n_words / 2 : 0;
   if (n2) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess)
-      (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     uint64_t tiles = (n2 + (uint64_t)kThreads * kUnroll - 1) / ((uint64_t)kThreads * kUnroll);
-    uint64_t cap = (uint64_t)cus * 8;
-    uint32_t blocks = (uint32_t)(tiles < cap ? tiles : cap);
+    uint32_t blocks = resident_blocks(tiles);
     hipLaunchKernelGGL(dense_max_kernel, dim3(blocks), dim3(kThreads), 0, stream, (u64x2*)self,
                        (const u64x2*)other, n2);
   }

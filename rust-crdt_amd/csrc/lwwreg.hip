@@ -37,6 +37,7 @@
 #include "csr_rank.h"
 #include "ctx.h"
 #include "kernels.h"
+#include "sched.h"
 
 namespace crdts_hip {
 namespace {
@@ -45,19 +46,10 @@ using namespace csr_rank;
 
 typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
 
-constexpr uint32_t kW = 64;
 constexpr uint32_t kBlock = 256;
 constexpr uint32_t kWaveMin = CRDT_LWWREG_WAVE_MIN_OPS;
 constexpr uint32_t kMaxReps = CRDT_LWWREG_MAX_REPS;
 
-__device__ __forceinline__ void fail(int* status, int code) { atomicCAS(status, 0, code); }
-
-uint32_t resident_blocks(uint64_t want) {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const uint64_t cap = (uint64_t)cus * 8;  // 8 blocks of 4 waves per CU
-  return (uint32_t)(want < cap ? want : cap);
-}
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
@@ -314,9 +306,9 @@ __device__ __forceinline__ Reg<MW> from_lane(const Reg<MW>& x, uint32_t src) {  
 template <int MW>
 __device__ __forceinline__ Reg<MW> of_lane(const Reg<MW>& x, uint32_t t) {  // readlane: t wave-uniform
   Reg<MW> y;
-  y.v = lane_u64(x.v, t);
-  y.m[0] = lane_u64(x.m[0], t);
-  if (MW > 1) y.m[MW - 1] = lane_u64(x.m[MW - 1], t);
+  y.v = lane64(x.v, t);
+  y.m[0] = lane64(x.m[0], t);
+  if (MW > 1) y.m[MW - 1] = lane64(x.m[MW - 1], t);
   return y;
 }
 
@@ -354,7 +346,7 @@ __global__ __launch_bounds__(kBlock) void apply_kernel(uint64_t* sval, uint64_t*
     while (pend) {
       const uint32_t t = (uint32_t)__builtin_ctzll(pend);
       pend &= pend - 1u;
-      const uint64_t bb = lane_u64(b, t), ee = lane_u64(e, t);
+      const uint64_t bb = lane64(b, t), ee = lane64(e, t);
       Reg<MW> carry = of_lane(s, t);  // the state before the chunk's first op
       uint32_t ne = 0;
       for (uint64_t j0 = bb; j0 < ee; j0 += kW) {

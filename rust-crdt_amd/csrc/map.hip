@@ -37,16 +37,6 @@ constexpr uint32_t kMpVals = 2u * kMapMvregMcap;  // kept values of one key (<= 
 static_assert(kMapMvregDcap <= kMpW, "lane d holds deferred entry d's set size");
 static_assert(kMapMvregDcap <= 0xFFu && kMapMvregMcap <= 0xFFu, "comb and vals pack an index into 8 bits");
 
-__device__ __forceinline__ void mp_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ bool set_has(const uint64_t* set, uint32_t n, uint64_t key, uint32_t lane) {
-  bool f = false;
-  for (uint32_t j = lane; j < n; j += kMpW) f = f || set[j] == key;
-  return __ballot(f) != 0ull;
-}
 
 // VS: each key's value clock rows (both sides) are staged in LDS with one
 // load per lane per side before the MVReg merge / truncate reads them (the
@@ -117,10 +107,10 @@ __global__ __launch_bounds__(kMpW, MINW) void map_mvreg_merge_kernel(crdt_map_mv
     // the map deferred sets (used entries) staged in LDS when they fit
     const uint32_t sS = S.scap, sO = O.scap;
     const bool st = (uint64_t)dS * sS + (uint64_t)dO * sO <= kMdStage;
-    mp_sync();  // the previous object's readers of md / mdn are done
+    sync();  // the previous object's readers of md / mdn are done
     mdn[0][lane] = dnS;
     mdn[1][lane] = dnO;
-    mp_sync();
+    sync();
     if (st) {
       for (uint32_t e = lane; e < dS * sS; e += kMpW) {
         const uint32_t d = e / sS;
@@ -154,7 +144,7 @@ __global__ __launch_bounds__(kMpW, MINW) void map_mvreg_merge_kernel(crdt_map_mv
         if (c >= 0) ++b;
       }
     }
-    mp_sync();
+    sync();
     // ---- entries, key by key in ascending order
     uint32_t nk = 0, a = 0, b = 0;
     bool over = false;
@@ -178,12 +168,12 @@ __global__ __launch_bounds__(kMpW, MINW) void map_mvreg_merge_kernel(crdt_map_mv
         if (lane + kMpW < n0) x1 = S.mv_clock[ia * S.mcap * A + lane + kMpW];
         if (lane < n1) y0 = O.mv_clock[ib * O.mcap * A + lane];
         if (lane + kMpW < n1) y1 = O.mv_clock[ib * O.mcap * A + lane + kMpW];
-        mp_sync();  // the previous key's reads of the stage are done
+        sync();  // the previous key's reads of the stage are done
         if (lane < n0) vr[0][lane] = x0;
         if (lane + kMpW < n0) vr[0][lane + kMpW] = x1;
         if (lane < n1) vr[1][lane] = y0;
         if (lane + kMpW < n1) vr[1][lane + kMpW] = y1;
-        mp_sync();
+        sync();
       }
       // value clock row v of this key on a side
       auto srow = [&](uint32_t v) -> Row<NS> {
@@ -202,7 +192,7 @@ __global__ __launch_bounds__(kMpW, MINW) void map_mvreg_merge_kernel(crdt_map_mv
         keep = vany(ec);
         del = vsub(cO, ec);
         for (uint32_t v = 0; v < ms; ++v) { if (lane == 0u) vals[nv] = v; ++nv; }
-        mp_sync();
+        sync();
       } else if (ho && !hs) {
         ec = vsub(eO, cS);
         keep = vany(ec);
@@ -222,7 +212,7 @@ __global__ __launch_bounds__(kMpW, MINW) void map_mvreg_merge_kernel(crdt_map_mv
           for (uint32_t w = 0; w < mo && !dom; ++w) dom = vstrict_less(sv, orow(w));
           if (!dom) { if (lane == 0u) vals[nv] = v; ++nv; }
         }
-        mp_sync();
+        sync();
         const uint32_t nkeep_s = nv;
         for (uint32_t w = 0; w < mo; ++w) {
           const Row<NS> ov = orow(w);
@@ -235,10 +225,10 @@ __global__ __launch_bounds__(kMpW, MINW) void map_mvreg_merge_kernel(crdt_map_mv
             dup = veq(q < nkeep_s ? srow(sl & 255u) : orow(sl & 255u), ov);
           }
           if (!dup) { if (lane == 0u) vals[nv] = 256u | w; ++nv; }
-          mp_sync();
+          sync();
         }
       }
-      mp_sync();
+      sync();
       // ---- apply_deferred on this key: every combined deferred clock naming it
       if (keep) {
         for (uint32_t c = 0; c < nc; ++c) {
@@ -286,7 +276,7 @@ __global__ __launch_bounds__(kMpW, MINW) void map_mvreg_merge_kernel(crdt_map_mv
           ++nk;
         }
       }
-      mp_sync();
+      sync();
       if (hs) ++a;
       if (ho) ++b;
     }
@@ -316,7 +306,7 @@ __global__ __launch_bounds__(kMpW, MINW) void map_mvreg_merge_kernel(crdt_map_mv
             if (o == 0) { at = q; break; }    // equal: this (later) one replaces it
             if (o < 0 && pos == ns) pos = q;  // insertion point
           }
-          mp_sync();
+          sync();
           if (at < ns) {
             if (lane == 0u) tk[at] = c;
           } else {
@@ -326,7 +316,7 @@ __global__ __launch_bounds__(kMpW, MINW) void map_mvreg_merge_kernel(crdt_map_mv
             }
             ++ns;
           }
-          mp_sync();
+          sync();
         }
         nw = ns;
       }
@@ -363,7 +353,7 @@ __global__ __launch_bounds__(kMpW, MINW) void map_mvreg_merge_kernel(crdt_map_mv
     }
     if (lane == 0u) R.n_def[ri] = nd;
     if (over && lane == 0u) atomicCAS(status, 0, CRDT_ECAPACITY);
-    mp_sync();
+    sync();
   }
 }
 

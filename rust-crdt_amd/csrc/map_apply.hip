@@ -23,7 +23,7 @@
 // consecutive iterations are ordered by each lane's own program order; the
 // per-key / per-entry counts (mv_n, dset_n) are read and written by lane 0
 // only. keys[] and dset[] are searched by all lanes: every edit ends in
-// mw_sync() (map_wave.h). The per-op edits are map_mvreg_ws.h's (shared with
+// sync() (map_wave.h). The per-op edits are map_mvreg_ws.h's (shared with
 // the nested map's op path, map_map_apply.hip, whose inner maps take them).
 // The ops are read through map_ops.h: headers, and the clock pairs of the
 // first ops, staged in LDS 64 ops at a time, each op's clock as a dense row.
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(kW, 7) void map_mvreg_apply_kernel(crdt_map_mvreg_s
     st.nk = nS;
     st.nd = dS;
     int err = 0;
-    mw_sync();
+    sync();
 
     uint64_t pb = 0ull;  // the staged pairs' first index
     for (uint64_t j = lo; j < hi && !err; ++j) {

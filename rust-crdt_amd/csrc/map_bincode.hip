@@ -31,16 +31,20 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/crdts_hip.h"
+#include "blob.h"
 #include "kernels.h"
 #include "map_limits.h"
 #include "sched.h"
+#include "wave.h"
 
 namespace crdts_hip {
 namespace {
 
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 
-constexpr uint32_t kW = 64;
+using namespace blob;  // Src, clock_cmp, wr (blob.h)
+using namespace wave;  // kW, sync, uni32 / uni64, scan_incl (wave.h)
+
 constexpr uint32_t kWaves = 4;       // waves per block
 constexpr uint32_t kStage = 4096;    // LDS window per wave: blobs of <= kStage - 32 bytes
 constexpr uint32_t kRowMax = kMapActorsMax;  // dense rows up to this many actors are built in LDS
@@ -71,25 +75,7 @@ struct Widths {
   uint32_t wa, wk, wv;  // actor, key, value bytes
 };
 
-__device__ __forceinline__ void wsync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ uint32_t uni32(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ uint64_t uni64(uint64_t v) {
-  return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32) |
-         (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v);
-}
-__device__ __forceinline__ uint32_t scan_incl(uint32_t v, uint32_t lane) {
-#pragma unroll
-  for (uint32_t d = 1; d < kW; d <<= 1) {
-    const uint32_t t = __shfl_up(v, d, kW);
-    v += lane >= d ? t : 0u;
-  }
-  return v;
-}
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
+__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
   for (uint32_t d = 32; d >= 1; d >>= 1) {
     const uint32_t lo = __shfl_xor((uint32_t)v, d, kW), hi = __shfl_xor((uint32_t)(v >> 32), d, kW);
     v += ((uint64_t)hi << 32) | lo;
@@ -97,35 +83,6 @@ __device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
   return v;
 }
 __device__ __forceinline__ bool fits(uint64_t x, uint32_t w) { return w >= 8u || x < (1ull << (8u * w)); }
-
-// Blob bytes as little-endian unsigned integers of w bytes at a blob position
-// (the caller has checked pos + w <= len). Window: b is the 16-B aligned LDS
-// base, the blob starts at b + d; a field is two aligned u64 reads and a
-// funnel shift (the window keeps 16 spare bytes past the blob). HBM: byte loads.
-template <bool WINDOW>
-struct Src;
-template <>
-struct Src<true> {
-  const uint8_t* b;
-  uint32_t d;
-  __device__ __forceinline__ uint64_t get(uint64_t pos, uint32_t w) const {
-    const uint32_t a = d + (uint32_t)pos;
-    const uint64_t* q = (const uint64_t*)(b + (a & ~7u));
-    const uint32_t sh = 8u * (a & 7u);
-    const uint64_t lo = q[0], hi = q[1];
-    const uint64_t v = sh ? (lo >> sh) | (hi << (64u - sh)) : lo;
-    return w >= 8u ? v : v & ((1ull << (8u * w)) - 1u);
-  }
-};
-template <>
-struct Src<false> {
-  const uint8_t* b;
-  __device__ __forceinline__ uint64_t get(uint64_t pos, uint32_t w) const {
-    uint64_t v = 0;
-    for (uint32_t i = 0; i < w; ++i) v |= (uint64_t)b[pos + i] << (8u * i);
-    return v;
-  }
-};
 
 // The aligned 16-B lines covering blob [off, off + len) of the buffer, into
 // the window; returns the blob's misalignment. A line that reaches outside
@@ -195,30 +152,14 @@ __device__ __forceinline__ bool put_clock(const SRC& B, uint64_t p, uint32_t n, 
     }
   }
   if (lds) {
-    wsync();
+    sync();
     for (uint32_t a = lane; a < A; a += kW) {
       dst[a] = row[a];
       row[a] = 0ull;
     }
-    wsync();
+    sync();
   }
   return bad;
-}
-
-// lexicographic (actor, counter) order of two bincode clocks, a proper prefix
-// first (CLOCK ORDER): -1, 0, 1
-template <class SRC>
-__device__ __forceinline__ int clock_cmp(const SRC& B, uint64_t pa, uint32_t na, uint64_t pb, uint32_t nb,
-                                         uint32_t wa) {
-  const uint32_t n = na < nb ? na : nb;
-  const uint64_t sa = wa + 8u;
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint64_t xa = B.get(pa + sa * i, wa), xb = B.get(pb + sa * i, wa);
-    if (xa != xb) return xa < xb ? -1 : 1;
-    const uint64_t ca = B.get(pa + sa * i + wa, 8), cb = B.get(pb + sa * i + wa, 8);
-    if (ca != cb) return ca < cb ? -1 : 1;
-  }
-  return na == nb ? 0 : (na < nb ? -1 : 1);
 }
 
 // One MVReg at p (the stand-alone register, or an entry's value): its values
@@ -303,7 +244,7 @@ __device__ __forceinline__ int ingest_map(const SRC& B, uint64_t& p, uint64_t le
   }
   if (whole && p != len) return CRDT_ENONCANON;  // trailing bytes
   if (nd) {
-    wsync();
+    sync();
     // rank by comparison count: lane d counts the clocks below clock d
     uint32_t r = 0;
     bool dup = false;
@@ -319,7 +260,7 @@ __device__ __forceinline__ int ingest_map(const SRC& B, uint64_t& p, uint64_t le
       X->Rd[lane] = r;
     }
     if (__ballot(dup)) return CRDT_ENONCANON;
-    wsync();
+    sync();
     for (uint32_t d = 0; d < (uint32_t)nd; ++d) {
       const uint64_t slot = i * R.dcap + uni32(X->Rd[d]);  // ranks are distinct and < nd
       const uint64_t pc = uni64(X->Pd[d]), ps = uni64(X->Ps[d]);
@@ -378,7 +319,7 @@ __global__ __launch_bounds__(kW* kWaves) void map_bincode_ingest_kernel(
   const uint32_t lane = threadIdx.x & (kW - 1u), wave = threadIdx.x / kW;
   WaveLds* X = &lds[wave];
   for (uint32_t a = lane; a < kRowMax; a += kW) X->row[a] = 0ull;
-  wsync();
+  sync();
   const uint64_t n_waves = (uint64_t)gridDim.x * kWaves;
   for (uint64_t i = (uint64_t)blockIdx.x * kWaves + wave; i < n_obj; i += n_waves) {
     const uint64_t off = uni64(boff[i]), len = uni64(blen[i]);
@@ -386,9 +327,9 @@ __global__ __launch_bounds__(kW* kWaves) void map_bincode_ingest_kernel(
     if (off > blob_bytes || len > blob_bytes - off) {
       rc = CRDT_ENONCANON;  // the blob is not inside the buffer: nothing of it is read
     } else if (len + 32u <= kStage) {
-      wsync();  // the previous object's window readers are done
+      sync();  // the previous object's window readers are done
       const uint32_t d = stage_blob(X->stage, blobs, blob_bytes, off, len, lane);
-      wsync();
+      sync();
       const Src<true> B{(const uint8_t*)X->stage, d};
       uint64_t p = 0;
       rc = MAP ? ingest_map(B, p, len, true, W, A, R, i, X, lane)
@@ -433,10 +374,6 @@ __device__ __forceinline__ uint32_t wave_row_nnz(const uint64_t* row, uint32_t A
     n += (uint32_t)__popcll(__ballot(nz));
   }
   return n;
-}
-
-__device__ __forceinline__ void wr(uint8_t* o, uint64_t pos, uint64_t v, uint32_t w) {
-  for (uint32_t i = 0; i < w; ++i) o[pos + i] = (uint8_t)(v >> (8u * i));
 }
 
 // The dense row as a bincode clock at o + q, every lane writing the pair of
@@ -521,7 +458,7 @@ __device__ __forceinline__ uint64_t map_size(const crdt_map_mvreg_slab& S, uint6
     for (uint32_t j = 0; j < ns; ++j) bad = bad || !fits(S.dset[slot * S.scap + j], W.wk);
     mine += 8u + sa * lane_row_nnz(S.dclock + slot * A, A, amax, bad) + 8u + (uint64_t)ns * W.wk;
   }
-  const uint64_t total = 24u + sa * wave_row_nnz(S.clock + i * A, A, amax, bad, lane) + wave_sum(mine);
+  const uint64_t total = 24u + sa * wave_row_nnz(S.clock + i * A, A, amax, bad, lane) + wave_sum64(mine);
   bad_out = __ballot(bad) != 0ull;
   return uni64(total);
 }
@@ -586,7 +523,7 @@ __device__ __forceinline__ uint64_t mvreg_size(const uint32_t* sn, const uint64_
     if (v < kW) first = sz;
     mine += sz;
   }
-  const uint64_t total = 8u + wave_sum(mine);
+  const uint64_t total = 8u + wave_sum64(mine);
   bad_out = __ballot(bad) != 0ull;
   return uni64(total);
 }
@@ -674,7 +611,7 @@ __device__ __forceinline__ int walk_deferred(const SRC& B, uint64_t& p, uint64_t
   uint64_t nd;
   if (!take_len(B, p, len, 16u, nd)) return CRDT_ENONCANON;
   if (nd > dcap || nd > LDS::kDef) return CRDT_ECAPACITY;
-  wsync();  // the table's earlier readers are done
+  sync();  // the table's earlier readers are done
   for (uint32_t d = 0; d < (uint32_t)nd; ++d) {
     uint32_t nc;
     if (!take_clock(B, p, len, wa, A, nc)) return CRDT_ENONCANON;
@@ -693,7 +630,7 @@ __device__ __forceinline__ int walk_deferred(const SRC& B, uint64_t& p, uint64_t
   }
   n = (uint32_t)nd;
   if (!nd) return 0;
-  wsync();
+  sync();
   bool dup = false;
   for (uint32_t d = lane; d < (uint32_t)nd; d += kW) {
     const uint64_t pm = X->Pd[d];
@@ -708,7 +645,7 @@ __device__ __forceinline__ int walk_deferred(const SRC& B, uint64_t& p, uint64_t
     X->Rd[d] = r;
   }
   if (__ballot(dup)) return CRDT_ENONCANON;
-  wsync();
+  sync();
   for (uint32_t d = 0; d < (uint32_t)nd; ++d) {
     const uint64_t slot = uni32(X->Rd[d]);  // ranks are distinct and < nd
     const uint64_t pc = uni64(X->Pd[d]), ps = uni64(X->Ps[d]);
@@ -768,7 +705,7 @@ __device__ __forceinline__ int ingest_obj(const SRC& B, uint64_t len, NWidths W,
     uint64_t nm;
     if (!take_len(B, p, len, wm + 8u, nm)) return CRDT_ENONCANON;
     if (nm > R.mcap || nm > kNestMax) return CRDT_ECAPACITY;
-    wsync();  // the table's earlier readers are done
+    sync();  // the table's earlier readers are done
     for (uint32_t j = 0; j < (uint32_t)nm; ++j) {
       if (len - p < wm) return CRDT_ENONCANON;
       const uint64_t x = B.get(p, wm);
@@ -782,7 +719,7 @@ __device__ __forceinline__ int ingest_obj(const SRC& B, uint64_t len, NWidths W,
       p += nc * sa;
     }
     if (nm) {
-      wsync();
+      sync();
       bool dup = false;
       for (uint32_t j = lane; j < (uint32_t)nm; j += kW) {
         const uint64_t x = X->Ps[j];
@@ -795,7 +732,7 @@ __device__ __forceinline__ int ingest_obj(const SRC& B, uint64_t len, NWidths W,
         X->Rd[j] = r;
       }
       if (__ballot(dup)) return CRDT_ENONCANON;  // two equal members
-      wsync();
+      sync();
       for (uint32_t j = 0; j < (uint32_t)nm; ++j) {
         const uint64_t ms = slot * R.mcap + uni32(X->Rd[j]);  // ranks are distinct and < nm
         bad = put_clock(B, uni64(X->Pd[j]), uni32(X->Ld[j]), wa, A, R.vmclock + ms * A, X->row, lane) || bad;
@@ -852,7 +789,7 @@ __device__ __forceinline__ int ingest_obj(const SRC& B, uint64_t len, NWidths W,
     if (!take_clock(B, p, len, wa, A, nc)) return CRDT_ENONCANON;
     bad = put_clock(B, p, nc, wa, A, R.eclock + slot * A, X->row, lane) || bad;
     p += nc * sa;
-    wsync();  // the table's earlier readers are done
+    sync();  // the table's earlier readers are done
     const int rc = ingest_map(B, p, len, false, Widths{wa, W.wx, W.wv}, A, R.inner, slot, X, lane);
     if (rc) return rc;
     if (lane == 0u) R.keys[slot] = key;
@@ -878,7 +815,7 @@ __global__ __launch_bounds__(kW* kWaves) void nested_bincode_ingest_kernel(
   const uint32_t lane = threadIdx.x & (kW - 1u), wave = threadIdx.x / kW;
   NestLds* X = &lds[wave];
   for (uint32_t a = lane; a < kRowMax; a += kW) X->row[a] = 0ull;
-  wsync();
+  sync();
   const uint64_t n_waves = (uint64_t)gridDim.x * kWaves;
   for (uint64_t i = (uint64_t)blockIdx.x * kWaves + wave; i < n_obj; i += n_waves) {
     const uint64_t off = uni64(boff[i]), len = uni64(blen[i]);
@@ -886,9 +823,9 @@ __global__ __launch_bounds__(kW* kWaves) void nested_bincode_ingest_kernel(
     if (off > blob_bytes || len > blob_bytes - off) {
       rc = CRDT_ENONCANON;  // the blob is not inside the buffer: nothing of it is read
     } else if (len + 32u <= kStage) {
-      wsync();  // the previous object's window readers are done
+      sync();  // the previous object's window readers are done
       const uint32_t d = stage_blob(X->stage, blobs, blob_bytes, off, len, lane);
-      wsync();
+      sync();
       rc = ingest_obj(Src<true>{(const uint8_t*)X->stage, d}, len, W, A, R, i, X, lane);
     } else {
       rc = ingest_obj(Src<false>{blobs + off}, len, W, A, R, i, X, lane);
@@ -982,7 +919,7 @@ __device__ __forceinline__ uint64_t obj_size(const crdt_map_orswot_slab& S, uint
   pairs += flat_nnz(S.vclock + i * S.kcap * A, nk, A, amax, bad, lane);
   if (wk < 8u)
     for (uint32_t k = lane; k < nk; k += kW) bad = bad || !fits(S.keys[i * S.kcap + k], wk);
-  const uint64_t total = fixed + wave_sum(mine + sa * pairs);
+  const uint64_t total = fixed + wave_sum64(mine + sa * pairs);
   bad_out = __ballot(bad) != 0ull;
   return uni64(total);
 }
@@ -1092,7 +1029,7 @@ __device__ __forceinline__ uint64_t obj_size(const crdt_map_map_slab& S, uint64_
   for (uint32_t k = 0; k < nk; ++k) inner_size(S.inner, i * S.kcap + k, WI, A, amax, fixed, pairs, mine, bad, lane);
   for (uint32_t d = lane; d < nd; d += kW)
     mine += lane_def_size(S.dclock, S.dset_n, S.dset, i * S.dcap + d, S.scap, A, W.wa, wk, amax, bad);
-  const uint64_t total = fixed + wave_sum(mine + sa * pairs);
+  const uint64_t total = fixed + wave_sum64(mine + sa * pairs);
   bad_out = __ballot(bad) != 0ull;
   return uni64(total);
 }

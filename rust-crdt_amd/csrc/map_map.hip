@@ -41,16 +41,6 @@ static_assert(kMapMapDcap <= 64u, "lane d holds outer deferred entry d's set siz
 constexpr uint32_t kMmStage = 128;  // u64: the map deferred sets staged per object when both sides fit
 constexpr uint64_t kMmNone = ~0ull;
 
-__device__ __forceinline__ void mm_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ bool set_has(const uint64_t* set, uint32_t n, uint64_t key, uint32_t lane) {
-  bool f = false;
-  for (uint32_t j = lane; j < n; j += kMmW) f = f || set[j] == key;
-  return __ballot(f) != 0ull;
-}
 
 // The outer pass. Writes R's outer part and, for output slot t = i * R.kcap + k,
 // tsrc[2t], tsrc[2t + 1] (the inner maps to merge: S row, O row, kMmNone when
@@ -85,10 +75,10 @@ __global__ __launch_bounds__(kMmW) void map_map_outer_kernel(crdt_map_map_slab S
         // the map deferred sets staged in LDS when they fit (map.hip)
         const uint32_t sS = S.scap, sO = O.scap;
         const bool st = (uint64_t)dS * sS + (uint64_t)dO * sO <= kMmStage;
-        mm_sync();  // the previous object's readers of md / mdn are done
+        sync();  // the previous object's readers of md / mdn are done
         mdn[0][lane] = dnS;
         mdn[1][lane] = dnO;
-        mm_sync();
+        sync();
         if (st) {
           for (uint32_t e = lane; e < dS * sS; e += kMmW) {
             const uint32_t d = e / sS;
@@ -120,7 +110,7 @@ __global__ __launch_bounds__(kMmW) void map_map_outer_kernel(crdt_map_map_slab S
             if (c >= 0) ++b;
           }
         }
-        mm_sync();
+        sync();
         // ---- entries, key by key in ascending order
         uint32_t a = 0, b = 0;
         while (a < nS || b < nO) {
@@ -219,7 +209,7 @@ __global__ __launch_bounds__(kMmW) void map_map_outer_kernel(crdt_map_map_slab S
       tsrc[2 * (i * R.kcap + k) + 1] = kMmNone;
     }
     if (over && lane == 0u) atomicCAS(status, 0, CRDT_ECAPACITY);
-    mm_sync();
+    sync();
   }
 }
 

@@ -96,7 +96,7 @@ __global__ __launch_bounds__(kW, NS == 1 ? 6 : 1) void map_map_apply_kernel(crdt
         uint32_t nd = dS;
         uint32_t nfree = 0u, nphys = 0u;  // freed slots on the stack; slots ever handed out
         nk = nS;
-        mw_sync();
+        sync();
 
         // the key slot's inner map as a scratch row (copied from self on its
         // first edit); ~0 with err set for a malformed self row
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(kW, NS == 1 ? 6 : 1) void map_map_apply_kernel(crdt
             return ~0ull;
           }
           if (lane == 0u) tsrc[pos] = kSrcWork | p;
-          mw_sync();
+          sync();
           return i * Rk + p;
         };
         // apply_rm's entry edit (:343-349): the key's entry clock loses D; an
@@ -136,7 +136,7 @@ __global__ __launch_bounds__(kW, NS == 1 ? 6 : 1) void map_map_apply_kernel(crdt
             shift_down(keys, pos, nk, lane);
             shift_down(tsrc, pos, nk, lane);
             --nk;
-            mw_sync();
+            sync();
             return;
           }
           strow<NS>(ecl + (uint64_t)pos * A, ec, A, lane);
@@ -162,7 +162,7 @@ __global__ __launch_bounds__(kW, NS == 1 ? 6 : 1) void map_map_apply_kernel(crdt
             const bool pin = pb < (uint64_t)P.n_clk && lane < (uint64_t)P.n_clk - pb;
             const uint32_t pa_ = pin ? P.clk_act[pb + lane] : 0u;
             const uint64_t pc_ = pin ? P.clk_ctr[pb + lane] : 0ull;
-            mw_sync();  // the previous chunk's reads of the stage are done
+            sync();  // the previous chunk's reads of the stage are done
             hkind[lane] = k_;
             hact[lane] = a_;
             hact2[lane] = a2_;
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(kW, NS == 1 ? 6 : 1) void map_map_apply_kernel(crdt
             hend[lane] = e_;
             pact[lane] = pa_;
             pctr[lane] = pc_;
-            mw_sync();
+            sync();
           }
           const uint32_t kind = uni32(hkind[t]);
           const uint64_t clo = t ? uni64(hend[t - 1u]) : pb, chi = uni64(hend[t]);
@@ -187,10 +187,10 @@ __global__ __launch_bounds__(kW, NS == 1 ? 6 : 1) void map_map_apply_kernel(crdt
           if (kind == CRDT_MAPMAP_OP_NOP) continue;
           // ---- the op's clock as a dense row (and its canonicity)
           const uint32_t np = (uint32_t)(chi - clo);
-          mw_sync();  // the previous op's reads of oc are done
+          sync();  // the previous op's reads of oc are done
           oc[lane] = 0ull;
           oc[lane + kW] = 0ull;
-          mw_sync();
+          sync();
           bool cbad = false;
           if (chi - pb <= kW) {  // its pairs are staged, from slot clo - pb (clo >= pb: checked op by op)
             const uint32_t f = (uint32_t)(clo - pb);
@@ -212,7 +212,7 @@ __global__ __launch_bounds__(kW, NS == 1 ? 6 : 1) void map_map_apply_kernel(crdt
             err = CRDT_ENONCANON;
             break;
           }
-          mw_sync();
+          sync();
           const Row<NS> C = ldrow<NS>(oc, A, lane);
 
           if (kind == CRDT_MAPMAP_OP_RM) {
@@ -287,7 +287,7 @@ __global__ __launch_bounds__(kW, NS == 1 ? 6 : 1) void map_map_apply_kernel(crdt
             if (err) break;
             map_close<NS>(m, st, A, lane);
           }
-          mw_sync();
+          sync();
           // ---- apply_deferred: every (clock, key) removed again; the clocks
           // the map clock still does not cover stay, with their sets
           uint32_t w = 0;
@@ -299,7 +299,7 @@ __global__ __launch_bounds__(kW, NS == 1 ? 6 : 1) void map_map_apply_kernel(crdt
             if (w != d) def_move<NS>(def, w, d, A, lane);
             ++w;
           }
-          if (w != nd) mw_sync();
+          if (w != nd) sync();
           nd = w;
         }
         if (!err) {
@@ -316,9 +316,9 @@ __global__ __launch_bounds__(kW, NS == 1 ? 6 : 1) void map_map_apply_kernel(crdt
       nk = 0u;
       if (lane == 0u) atomicCAS(status, 0, err);
     }
-    mw_sync();
+    sync();
     for (uint32_t k = nk + lane; k < Rk; k += kW) tsrc[k] = kSrcNone;
-    mw_sync();
+    sync();
   }
 }
 

@@ -8,7 +8,7 @@
 // mappings: a clock row by the lane of its actor slot (ldrow / strow); a
 // block of elements by lane e % 64 (copy_n); the per-key / per-entry counts
 // (mv_n, dset_n) and single values by lane 0. An address is used under one
-// mapping between two mw_sync() and every edit ends in one, so a lane's own
+// mapping between two sync() and every edit ends in one, so a lane's own
 // program order covers the rest. keys[] and dset[] are searched by all lanes.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -70,7 +70,7 @@ __device__ inline void map_close(const MapRef& m, const MapSt<NS>& st, uint32_t 
     *m.n_keys = st.nk;
     *m.n_def = st.nd;
   }
-  mw_sync();
+  sync();
 }
 // an empty map in row `m`
 template <int NS>
@@ -83,7 +83,7 @@ __device__ inline void map_clear(const MapRef& m, uint32_t A, uint32_t lane) {
 
 // Row srow of S -> row rrow of R, used slots only (R's capacities >= S's).
 // false, and nothing written, for a row the merge rejects (a count above its
-// capacity). Ends in mw_sync().
+// capacity). Ends in sync().
 __device__ inline bool map_copy_row(const crdt_map_mvreg_slab& S, uint64_t srow, const crdt_map_mvreg_slab& R,
                                     uint64_t rrow, uint32_t A, uint32_t lane) {
   const uint32_t nS = uni32(S.n_keys[srow]), dS = uni32(S.n_def[srow]);
@@ -116,7 +116,7 @@ __device__ inline bool map_copy_row(const crdt_map_mvreg_slab& S, uint64_t srow,
     *m.n_keys = nS;
     *m.n_def = dS;
   }
-  mw_sync();
+  sync();
   return true;
 }
 
@@ -155,7 +155,7 @@ __device__ inline void map_rm_entry(const MapRef& m, MapSt<NS>& st, uint64_t key
     }
     if (lane == 0u) m.mvn[pos] = w;
   }
-  mw_sync();
+  sync();
 }
 
 // Op::Rm -> apply_rm (src/map.rs:336-350). 0, or CRDT_ECAPACITY.
@@ -229,7 +229,7 @@ __device__ inline int map_up(const MapRef& m, MapSt<NS>& st, uint32_t da, uint64
     n = w;
   }
   if (lane == 0u) m.mvn[pos] = n;
-  mw_sync();
+  sync();
   // apply_deferred (:325-333): every (clock, key) removed again; the clocks
   // the map clock still does not cover stay, with their sets (a subsequence
   // of a CLOCK ORDER list is in CLOCK ORDER)
@@ -243,7 +243,7 @@ __device__ inline int map_up(const MapRef& m, MapSt<NS>& st, uint32_t da, uint64
     if (w != e) def_move<NS>(d, w, e, A, lane);
     ++w;
   }
-  if (w != st.nd) mw_sync();
+  if (w != st.nd) sync();
   st.nd = w;
   return 0;
 }
@@ -305,7 +305,7 @@ __device__ inline void map_truncate(const MapRef& m, MapSt<NS>& st, const Row<NS
   }
   st.nd = wd;
   st.cM = vsub(st.cM, T);
-  mw_sync();
+  sync();
 }
 
 // ---- Map::truncate from one slab row into another (source != destination):
@@ -319,13 +319,13 @@ __device__ inline void map_truncate(const MapRef& m, MapSt<NS>& st, const Row<NS
 // subtract) stays. The order is worked out on source indices in `ord` (LDS, n
 // slots; the wave's own) and every kept entry is then written once, its used
 // slots only. Returns the count written. Every set size must be <= sRs. Ends
-// in mw_sync().
+// in sync().
 template <int NS>
 __device__ inline uint32_t def_truncate_to(const uint64_t* sdcl, const uint32_t* sdsn, const uint64_t* sdse,
                                            uint32_t sRs, uint32_t n, const DefRef& d, const Row<NS>& T, uint32_t* ord,
                                            uint32_t A, uint32_t lane) {
   uint32_t wd = 0;
-  mw_sync();  // the previous list's readers of ord are done
+  sync();  // the previous list's readers of ord are done
   for (uint32_t e = 0; e < n; ++e) {
     const Row<NS> D = vsub(ldrow<NS>(sdcl + (uint64_t)e * A, A, lane), T);
     if (!vany(D)) continue;
@@ -342,7 +342,7 @@ __device__ inline uint32_t def_truncate_to(const uint64_t* sdcl, const uint32_t*
       --p;
     }
     if (dup) {
-      mw_sync();
+      sync();
       if (lane == 0u) ord[p - 1u] = e;  // it takes the equal clock's place
     } else {
       for (uint32_t hi = wd; hi > p;) {  // the ones above it one slot up, the last 64 first
@@ -350,15 +350,15 @@ __device__ inline uint32_t def_truncate_to(const uint64_t* sdcl, const uint32_t*
         const uint32_t k = lo + lane;
         uint32_t x = 0u;
         if (k < hi) x = ord[k];
-        mw_sync();
+        sync();
         if (k < hi) ord[k + 1u] = x;
-        mw_sync();
+        sync();
         hi = lo;
       }
       if (lane == 0u) ord[p] = e;
       ++wd;
     }
-    mw_sync();
+    sync();
   }
   for (uint32_t j = 0; j < wd; ++j) {
     const uint32_t e = uni32(ord[j]);
@@ -367,7 +367,7 @@ __device__ inline uint32_t def_truncate_to(const uint64_t* sdcl, const uint32_t*
     copy_n(d.dse + (uint64_t)j * d.Rs, sdse + (uint64_t)e * sRs, sn, lane);
     if (lane == 0u) d.dsn[j] = sn;
   }
-  mw_sync();
+  sync();
   return wd;
 }
 
@@ -375,7 +375,7 @@ __device__ inline uint32_t def_truncate_to(const uint64_t* sdcl, const uint32_t*
 // R's capacities >= S's and R != S: map_truncate's forward compaction with the
 // reads on S and the writes on R (slot w <= k), so nothing is written twice.
 // `ord`: S.dcap LDS slots (def_truncate_to). false, and nothing written, for a
-// row the merge rejects (a count above its capacity). Ends in mw_sync().
+// row the merge rejects (a count above its capacity). Ends in sync().
 template <int NS>
 __device__ inline bool map_truncate_to(const crdt_map_mvreg_slab& S, uint64_t srow, const crdt_map_mvreg_slab& R,
                                        uint64_t rrow, const Row<NS>& T, uint32_t* ord, uint32_t A, uint32_t lane) {

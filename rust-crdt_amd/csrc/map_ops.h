@@ -52,7 +52,7 @@ __device__ __forceinline__ uint64_t refill(const OpStage& s, const Ops& P, const
   const bool pin = pb < (uint64_t)P.n_clk && lane < (uint64_t)P.n_clk - pb;
   const uint32_t pa_ = pin ? P.clk_act[pb + lane] : 0u;
   const uint64_t pc_ = pin ? P.clk_ctr[pb + lane] : 0ull;
-  mw_sync();  // the previous chunk's reads of the stage are done
+  sync();  // the previous chunk's reads of the stage are done
   s.hkind[lane] = k_;
   s.hact[lane] = a_;
   s.hkey[lane] = y_;
@@ -61,7 +61,7 @@ __device__ __forceinline__ uint64_t refill(const OpStage& s, const Ops& P, const
   s.hend[lane] = e_;
   s.pact[lane] = pa_;
   s.pctr[lane] = pc_;
-  mw_sync();
+  sync();
   return pb;
 }
 
@@ -97,10 +97,10 @@ __device__ __forceinline__ OpClock<NS> read_clock(const OpStage& s, const Ops& P
                                                   uint32_t A, uint32_t lane) {
   const uint64_t clo = h.clo, chi = h.chi;
   const uint32_t np = (uint32_t)(chi - clo);
-  mw_sync();  // the previous op's reads of oc are done
+  sync();  // the previous op's reads of oc are done
   s.oc[lane] = 0ull;
   s.oc[lane + kW] = 0ull;
-  mw_sync();
+  sync();
   bool cbad = false;
   if (chi - pb <= kW) {  // its pairs are staged, from slot clo - pb (clo >= pb: checked op by op)
     const uint32_t f = (uint32_t)(clo - pb);
@@ -119,7 +119,7 @@ __device__ __forceinline__ OpClock<NS> read_clock(const OpStage& s, const Ops& P
     }
   }
   if (__ballot(cbad) != 0ull) return {zrow<NS>(), false};
-  mw_sync();
+  sync();
   return {ldrow<NS>(s.oc, A, lane), true};
 }
 

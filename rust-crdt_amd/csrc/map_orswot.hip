@@ -40,12 +40,6 @@ using namespace mows;  // the LDS nested-set workspace, its apply_deferred and t
 constexpr uint32_t kMoLdsMax = 65536;  // workspace limit per wave
 constexpr uint32_t kMoStageMax = 16384;  // map deferred staging area limit per wave
 
-__device__ __forceinline__ bool set_has(const uint64_t* set, uint32_t n, uint64_t key, uint32_t lane) {
-  bool f = false;
-  for (uint32_t j = lane; j < n; j += kW) f = f || set[j] == key;
-  return __ballot(f) != 0ull;
-}
-
 // dst[e] = at(e) for e < n, all lanes: 16-B non-temporal stores when dst is
 // 16-B aligned and n even, 8-B stores otherwise.
 typedef uint64_t mo_u64x2 __attribute__((ext_vector_type(2)));
@@ -66,7 +60,7 @@ __device__ __forceinline__ void fill64(uint64_t* dst, uint64_t n, uint32_t lane,
 // the key walk's registers), then every array (ws_copy: each load
 // independent of the others' results — the deferred sets copied
 // capacity-strided, their sizes by one lane each — so both sides' slots cost
-// one round trip), then the caller's mw_sync.
+// one round trip), then the caller's sync().
 __device__ __forceinline__ void ws_counts(Ws& W, const crdt_map_orswot_slab& X, uint64_t ki, uint32_t k, uint32_t vm,
                                           uint32_t vd) {
   // key k's counts: lane k of the registers the key walk loaded (k < 64)
@@ -153,7 +147,7 @@ __device__ void ws_merge(const Ws& Wc, const Ws& Wo, Ws& Wn, Row<NS>& sclk, Row<
   }
   Wn.nd = nd;
   sclk = vmax(sclk, oclk);  // :153
-  mw_sync();
+  sync();
   ws_apply_deferred(Wn, sclk, mdead, ddead, c, lane);  // :155
 }
 
@@ -226,7 +220,7 @@ __global__ __launch_bounds__(kW, MINW) void map_orswot_merge_kernel(crdt_map_ors
   W1.dn = W0.dn + S.vdcap;
   W2.dn = W1.dn + c.DW;
   uint32_t* const ddead = mdead + c.MW;
-  mw_sync();
+  sync();
   BlockTickets<4> sched(n_obj, ctl + 3, lane);  // (sched.h)
   for (uint64_t i = sched.first(); i < n_obj; i = sched.next(i)) {
     const Row<NS> cS = rowv<NS>(S.clock, i, A, lane), cO = rowv<NS>(O.clock, i, A, lane);
@@ -284,7 +278,7 @@ __global__ __launch_bounds__(kW, MINW) void map_orswot_merge_kernel(crdt_map_ors
       if (lane == 0u) atomicCAS(status, 0, CRDT_ENONCANON);
       continue;
     }
-    mw_sync();
+    sync();
     // the map deferred sets staged in LDS when they fit (md_cap words): the
     // key loop asks each of them about every key. (Staging their clocks too
     // cost more occupancy than the round trips it saved: DESIGN.md §9.)
@@ -302,7 +296,7 @@ __global__ __launch_bounds__(kW, MINW) void map_orswot_merge_kernel(crdt_map_ors
         if (e - d * sO < mdn1[d]) mdO[e] = O.dset[i * O.dcap * sO + e];
       }
     }
-    mw_sync();
+    sync();
     auto sdc = [&](uint32_t a) -> Row<NS> { return rowv<NS>(S.dclock, i * S.dcap + a, A, lane); };
     auto odc = [&](uint32_t b) -> Row<NS> { return rowv<NS>(O.dclock, i * O.dcap + b, A, lane); };
     // ---- combined map deferred list: self's, plus other's that self's clock does not cover
@@ -322,7 +316,7 @@ __global__ __launch_bounds__(kW, MINW) void map_orswot_merge_kernel(crdt_map_ors
         if (o >= 0) ++b;
       }
     }
-    mw_sync();
+    sync();
     auto comb_clock = [&](uint32_t e) -> Row<NS> {
       const uint32_t sa = e & 0xFFFFu, sb = e >> 16;
       return sa ? sdc(sa - 1u) : odc(sb - 1u);
@@ -342,7 +336,7 @@ __global__ __launch_bounds__(kW, MINW) void map_orswot_merge_kernel(crdt_map_ors
           ++nn;
         }
       }
-      mw_sync();
+      sync();
       return nn;
     };
     // ---- entries, key by key in ascending order
@@ -393,7 +387,7 @@ __global__ __launch_bounds__(kW, MINW) void map_orswot_merge_kernel(crdt_map_ors
         if (cho) ws_counts(W2, O, ib, cb, vmO, vdO);
         if (chs) ws_copy(W0, S, ia, c, lane);
         if (cho) ws_copy(W2, O, ib, c, lane);
-        mw_sync();
+        sync();
         Row<NS> vclk = chs ? vS : vO;
         Ws Wk = chs ? W0 : W2;
         if (chs && cho) {
@@ -413,7 +407,7 @@ __global__ __launch_bounds__(kW, MINW) void map_orswot_merge_kernel(crdt_map_ors
         } else {
           over = true;
         }
-        mw_sync();
+        sync();
       }
     }
     if (lane == 0u) R.n_keys[i] = nk;
@@ -449,7 +443,7 @@ __global__ __launch_bounds__(kW, MINW) void map_orswot_merge_kernel(crdt_map_ors
     }
     if (lane == 0u) R.n_def[i] = nd;
     if (over && lane == 0u) atomicCAS(status, 0, CRDT_ECAPACITY);
-    mw_sync();
+    sync();
   }
 }
 

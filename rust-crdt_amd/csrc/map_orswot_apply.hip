@@ -68,7 +68,7 @@ __global__ __launch_bounds__(kW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel(
   uint32_t* const ddead = W.dn + Rv;
   uint32_t* const mdead = ddead + Rv;
   for (uint32_t j = lane; j < R.vdcap + R.mcap; j += kW) ddead[j] = 0u;
-  mw_sync();
+  sync();
   BlockTickets<4> sched(n_obj, ctl + 3, lane);
   for (uint64_t i = sched.first(); i < n_obj; i = sched.next(i)) {
     // ---- the input row, checked as the merge checks it (map_orswot.hip)
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(kW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel(
     // searching out[i] itself)
     bool kvalid = nS <= kW;
     if (kvalid && lane < nS) lk[lane] = S.keys[i * S.kcap + lane];
-    mw_sync();
+    sync();
     auto find_map_key = [&](uint64_t key, uint32_t& pos) -> bool {
       if (!kvalid) return find_key(keys, nk, key, lane, pos);
       const uint64_t x = lane < nk ? lk[lane] : ~0ull;
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(kW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel(
         const uint32_t d = e / W.sw;
         if (e - d * W.sw < W.dn[d]) vds[p * Rv * Rvs + e] = W.dset[e];
       }
-      mw_sync();
+      sync();
     };
     auto flush = [&]() {
       if (cur != kNone && dirty) store_entry();
@@ -195,7 +195,7 @@ __global__ __launch_bounds__(kW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel(
       copy_n(W.dn, (const uint32_t*)(vdn + p * Rv), W.nd, lane);
       // capacity-strided (the workspace's stride is out's): no wait for the sizes
       copy_n(W.dset, (const uint64_t*)(vds + p * Rv * Rvs), W.nd * W.sw, lane);
-      mw_sync();
+      sync();
     };
     // key slot src of out[i] to slot dst (its used part); the slot is not the staged one
     auto move_slot = [&](uint32_t dst_, uint32_t src_) {
@@ -215,7 +215,7 @@ __global__ __launch_bounds__(kW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel(
         vnm[dst] = m;
         vnd[dst] = dn;
       }
-      mw_sync();  // the next slot's copy overwrites what other lanes read here
+      sync();  // the next slot's copy overwrites what other lanes read here
     };
 
     // apply_rm's entry edit (src/map.rs:341-349): the key's entry clock loses
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(kW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel(
         shift_down(keys, pos, nk, lane);
         if (kvalid) shift_down(lk, pos, nk, lane);
         --nk;
-        mw_sync();
+        sync();
         return;
       }
       acquire(pos);
@@ -273,7 +273,7 @@ __global__ __launch_bounds__(kW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel(
             copy_n(W.dset + (d + 1u) * W.sw, (const uint64_t*)(W.dset + d * W.sw), sn, lane);
             strow<NS>(W.dclk + (d + 1u) * A, r, A, lane);
             if (lane == 0u) W.dn[d + 1u] = sn;
-            mw_sync();
+            sync();
           }
           strow<NS>(W.dclk + at * A, C, A, lane);
           if (lane == 0u) {
@@ -282,7 +282,7 @@ __global__ __launch_bounds__(kW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel(
           }
           ++W.nd;
         }
-        mw_sync();
+        sync();
       }
       uint32_t mp;
       if (find_key(W.key, W.nm, member, lane, mp)) {
@@ -297,7 +297,7 @@ __global__ __launch_bounds__(kW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel(
           shift_down(W.key, mp, W.nm, lane);
           --W.nm;
         }
-        mw_sync();
+        sync();
       }
       return true;
     };
@@ -327,7 +327,7 @@ __global__ __launch_bounds__(kW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel(
         vc.v[s] = dc;
       }
       strow<NS>(W.row + mp * A, r, A, lane);
-      mw_sync();
+      sync();
       if (W.nd) ws_apply_deferred<NS>(W, vc, mdead, ddead, c, lane);
       return true;
     };
@@ -391,7 +391,7 @@ __global__ __launch_bounds__(kW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel(
           if (lane == 0u) lk[pos] = key;
         }
         ++nk;
-        mw_sync();
+        sync();
         cur = pos;  // an empty clock and an empty set, in the workspace only
         ec = zrow<NS>();
         vc = zrow<NS>();
@@ -419,7 +419,7 @@ __global__ __launch_bounds__(kW, NS == 1 ? 5 : 4) void map_orswot_apply_kernel(
         if (w != d) def_move<NS>(def, w, d, A, lane);
         ++w;
       }
-      if (w != nd) mw_sync();
+      if (w != nd) sync();
       nd = w;
     }
     if (err) {

@@ -52,14 +52,14 @@ __device__ void ws_apply_deferred(Ws& W, Row<NS> clk, uint32_t* mdead, uint32_t*
       const Row<NS> r = vsub(ldrow<NS>(W.row + lo * c.A, c.A, lane), D);
       strow(W.row + lo * c.A, r, c.A, lane);
       const bool gone = !vany(r);
-      mw_sync();
+      sync();
       if (gone && lane == 0u) mdead[lo] = 1u;
-      mw_sync();
+      sync();
     }
     const bool drop = vle(D, clk);
     if (lane == 0u) ddead[d] = drop ? 1u : 0u;
   }
-  mw_sync();
+  sync();
   // compaction, in place (destination <= source)
   uint32_t k = 0;
   for (uint32_t j = 0; j < W.nm; ++j) {
@@ -67,10 +67,10 @@ __device__ void ws_apply_deferred(Ws& W, Row<NS> clk, uint32_t* mdead, uint32_t*
     if (k != j) {
       const uint64_t key = W.key[j];
       const Row<NS> r = ldrow<NS>(W.row + j * c.A, c.A, lane);
-      mw_sync();
+      sync();
       if (lane == 0u) W.key[k] = key;
       strow(W.row + k * c.A, r, c.A, lane);
-      mw_sync();
+      sync();
     }
     ++k;
   }
@@ -81,18 +81,18 @@ __device__ void ws_apply_deferred(Ws& W, Row<NS> clk, uint32_t* mdead, uint32_t*
     if (k != d) {
       const Row<NS> D = ldrow<NS>(W.dclk + d * c.A, c.A, lane);
       const uint32_t n = uni32(W.dn[d]);
-      mw_sync();
+      sync();
       strow(W.dclk + k * c.A, D, c.A, lane);
       if (lane == 0u) W.dn[k] = n;
       for (uint32_t j = lane; j < n; j += kW) W.dset[k * W.sw + j] = W.dset[d * W.sw + j];  // (rows k < d)
-      mw_sync();
+      sync();
     }
     ++k;
   }
   W.nd = k;
   for (uint32_t j = lane; j < c.MW; j += kW) mdead[j] = 0u;
   for (uint32_t j = lane; j < c.DW; j += kW) ddead[j] = 0u;
-  mw_sync();
+  sync();
 }
 
 // Orswot::truncate (src/orswot.rs:159-172) of W (top clock `clk`) by `t`.
@@ -106,12 +106,12 @@ __device__ void ws_truncate(Ws& W, Row<NS>& clk, Row<NS> t, uint32_t* mdead, uin
     if (covered && lane == 0u) mdead[j] = 1u;
   }
   clk = vmax(clk, t);
-  mw_sync();
+  sync();
   ws_apply_deferred(W, clk, mdead, ddead, c, lane);
   // forget t from the top clock and every member clock (an emptied member stays)
   clk = vsub(clk, t);
   for (uint32_t j = 0; j < W.nm; ++j) strow(W.row + j * c.A, vsub(ldrow<NS>(W.row + j * c.A, c.A, lane), t), c.A, lane);
-  mw_sync();
+  sync();
 }
 
 }  // namespace mows

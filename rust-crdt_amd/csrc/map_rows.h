@@ -2,19 +2,19 @@
 // lane l is actor l + 64 s, NS slots per lane (NS = 1 for n_actors <= 64, 2
 // for <= 128), so every VClock operation is NS lane-parallel ops plus a
 // ballot. Reference: src/vclock.rs (subtract :236-242, merge :131-137,
-// PartialOrd :59-71, intersection :219-228).
+// PartialOrd :59-71, intersection :219-228). Namespace maprow also opens the
+// wave toolkit (wave.h) to the Map kernels; vorder reads lanes with its lane64.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "wave.h"
+
 namespace crdts_hip {
 namespace maprow {
 
-__device__ __forceinline__ uint64_t lane64(uint64_t v, uint32_t t) {
-  return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)(v >> 32), t) << 32) |
-         (uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)v, t);
-}
+using namespace wave;  // one wave per block in every Map kernel: kW, sync, uni32 / uni64, lane64, set_has
 
 template <int NS>
 struct Row {

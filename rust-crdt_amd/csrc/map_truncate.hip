@@ -144,7 +144,7 @@ __global__ __launch_bounds__(kW) void map_orswot_truncate_kernel(crdt_map_orswot
   uint32_t* const ddead = W.dn + Sv;
   uint32_t* const mdead = ddead + Sv;
   for (uint32_t j = lane; j < S.vdcap + S.mcap; j += kW) ddead[j] = 0u;
-  mw_sync();
+  sync();
   BlockTickets<4> sched(n_obj, ctl + 3, lane);
   for (uint64_t i = sched.first(); i < n_obj; i = sched.next(i)) {
     // ---- the input row, checked as the merge checks it (map_orswot.hip)
@@ -186,7 +186,7 @@ __global__ __launch_bounds__(kW) void map_orswot_truncate_kernel(crdt_map_orswot
         const uint32_t d = e / W.sw;
         if (e - d * W.sw < S.vdset_n[sk * Sv + d]) W.dset[e] = S.vdset[sk * Sv * Svs + e];
       }
-      mw_sync();
+      sync();
       mows::ws_truncate<NS>(W, vc, T, mdead, ddead, c, lane);
       // ---- out key slot w
       strow<NS>(R.eclock + rw * A, ec, A, lane);
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(kW) void map_orswot_truncate_kernel(crdt_map_orswot
         const uint32_t d = e / W.sw, o = e - d * W.sw;
         if (o < W.dn[d]) R.vdset[(rw * Rv + d) * Rvs + o] = W.dset[e];
       }
-      mw_sync();  // the next key's stage overwrites what other lanes read here
+      sync();  // the next key's stage overwrites what other lanes read here
       ++w;
     }
     const DefRef def = def_ref(R, i, A);

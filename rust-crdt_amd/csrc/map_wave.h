@@ -1,9 +1,10 @@
-// The wave-edit toolkit of the Map kernels (internal): what one wave needs to
-// edit the sorted arrays of a Map slab row in place — the wave fence, uniform
-// reads, block copies, one-slot shifts, the key search, and a map's deferred
-// removes (clocks in CLOCK ORDER with their key sets). Lane = actor slot
-// (map_rows.h, which also has lane64). Used by map_mvreg_ws.h,
-// map_orswot_ws.h, map_ops.h and the apply / truncate kernels built on them.
+// The slab-edit toolkit of the Map kernels (internal): what one wave needs to
+// edit the sorted arrays of a Map slab row in place — lane-0 reads, block
+// copies, one-slot shifts, the key search, and a map's deferred removes
+// (clocks in CLOCK ORDER with their key sets). Lane = actor slot (map_rows.h);
+// the wave fence, the uniform and cross-lane reads and kW are wave.h's, seen
+// through namespace maprow. Used by map_mvreg_ws.h, map_orswot_ws.h, map_ops.h
+// and the apply / truncate kernels built on them.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,18 +14,6 @@
 namespace crdts_hip {
 namespace maprow {
 
-constexpr uint32_t kW = 64;  // the wave width: one wave per block in every Map kernel
-
-// wave-local fence + barrier: every cross-lane edit ends in one
-__device__ __forceinline__ void mw_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ uint32_t uni32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ uint64_t uni64(uint64_t v) {
-  return ((uint64_t)uni32((uint32_t)(v >> 32)) << 32) | (uint64_t)uni32((uint32_t)v);
-}
 // a value only lane 0 ever touches
 __device__ __forceinline__ uint32_t cnt0(const uint32_t* p, uint32_t lane) {
   uint32_t x = 0u;
@@ -49,9 +38,9 @@ __device__ inline void shift_up(uint64_t* a, uint32_t p, uint32_t n, uint32_t la
     const uint32_t k = lo + lane;
     uint64_t x = 0ull;
     if (k < hi) x = a[k];
-    mw_sync();
+    sync();
     if (k < hi) a[k + 1u] = x;
-    mw_sync();
+    sync();
     hi = lo;
   }
 }
@@ -60,9 +49,9 @@ __device__ inline void shift_down(uint64_t* a, uint32_t p, uint32_t n, uint32_t 
     const uint32_t k = lo + lane;
     uint64_t x = 0ull;
     if (k < n) x = a[k];
-    mw_sync();
+    sync();
     if (k < n) a[k - 1u] = x;
-    mw_sync();
+    sync();
   }
 }
 // `key` in the ascending a[0, n): pos = how many are below it; is it there?
@@ -156,7 +145,7 @@ __device__ inline int def_insert(const DefRef& d, uint32_t& nd, uint64_t key, co
     }
     ++nd;
   }
-  mw_sync();
+  sync();
   return 0;
 }
 

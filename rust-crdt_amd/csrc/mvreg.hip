@@ -15,17 +15,15 @@
 
 #include "../../include/crdts_hip.h"
 #include "kernels.h"
+#include "sched.h"
+#include "wave.h"
 
 namespace crdts_hip {
 namespace {
 
-constexpr uint32_t kMW = 64;
+using namespace wave;  // sync (wave.h)
 
-__device__ __forceinline__ void mv_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+constexpr uint32_t kMW = 64;
 
 // G lanes per pair (G = power of two <= 64); each lane compares a strided
 // share of the A slots, the group's flags are combined from two ballots.
@@ -107,12 +105,12 @@ __global__ __launch_bounds__(256) void mvreg_merge_kernel(
       if (lane == 0u) atomicCAS(status, 0, CRDT_ENONCANON);
       continue;
     }
-    mv_sync();
+    sync();
     if (lane < ns * A) S[lane] = cS;
     if (lane < no * A) O[lane] = cO;
     for (uint32_t k = kMW + lane; k < ns * A; k += kMW) S[k] = sclk[o * scap * A + k];
     for (uint32_t k = kMW + lane; k < no * A; k += kMW) O[k] = oclk[o * ocap * A + k];
-    mv_sync();
+    sync();
     {  // flag matrices: G lanes per clock pair (G | 64, wave-uniform), strided over the actors, OR-reduced
       const uint32_t P1 = ns * no, P = P1 + no * no;
       uint32_t G = 1;
@@ -149,7 +147,7 @@ __global__ __launch_bounds__(256) void mvreg_merge_kernel(
         }
       }
     }
-    mv_sync();
+    sync();
     // self i: kept unless some other clock strictly dominates it (flags == "only <")
     bool ks = false, ko = false;
     if (lane < ns) {
@@ -180,7 +178,7 @@ __global__ __launch_bounds__(256) void mvreg_merge_kernel(
     if (ks) outval[o * outcap + rs] = cVs;
     if (ko) outval[o * outcap + ro] = cVo;
     for (uint32_t k = nk + lane; k < outcap; k += kMW) outval[o * outcap + k] = 0u;
-    mv_sync();
+    sync();
     uint64_t* oc = outclk + o * (uint64_t)AO;
     uint32_t k = lane / A, x = lane % A;  // slot and actor of this lane's first element
     const uint32_t dk = kMW / A, dx = kMW % A;  // per step of 64 elements
@@ -227,13 +225,13 @@ __global__ __launch_bounds__(kMW) void mvreg_merge_big_kernel(
     const uint64_t* O = oclk + o * ocap * A;
     // self i: kept unless some other clock strictly dominates it
     uint32_t nks = 0u;
-    mv_sync();  // the previous pair's readers of ks_s are done
+    sync();  // the previous pair's readers of ks_s are done
     for (uint32_t i = lane; i < ns; i += kMW) {
       bool k = true;
       for (uint32_t j = 0; j < no && k; ++j) k = mv_cmp_rows(S + (uint64_t)i * A, O + (uint64_t)j * A, A) != 2u;
       ks_s[i] = k ? 1u : 0u;
     }
-    mv_sync();
+    sync();
     for (uint32_t i = lane; i < ns; i += kMW) nks += ks_s[i];
     // other j: kept unless a self clock strictly dominates it, it equals a kept
     // self clock, or it equals an earlier other clock
@@ -255,7 +253,7 @@ __global__ __launch_bounds__(kMW) void mvreg_merge_big_kernel(
       if (lane == 0u) atomicCAS(status, 0, CRDT_ECAPACITY);
       continue;
     }
-    mv_sync();
+    sync();
     // survivors in order, one row per lane-round; then the unused slots zeroed
     uint64_t* oc = outclk + o * (uint64_t)outcap * A;
     uint32_t pos = 0u;
@@ -283,10 +281,8 @@ int launch_vclock_cmp(const uint64_t* a, const uint64_t* b, uint64_t n, uint32_t
   if (n == 0) return CRDT_OK;
   uint32_t G = 1;
   while (G < 64u && G * 2u <= A) G *= 2u;  // ~one or two slots per lane
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const uint64_t per_block = 4u * (kMW / G), want = (n + per_block - 1) / per_block, cap = (uint64_t)cus * 16u;
-  const uint32_t blocks = (uint32_t)(want < cap ? want : cap);
+  const uint64_t per_block = 4u * (kMW / G);
+  const uint32_t blocks = resident_blocks((n + per_block - 1) / per_block, 16u);
   hipLaunchKernelGGL(vclock_cmp_kernel, dim3(blocks), dim3(256), 0, stream, a, b, n, A, G, out);
   return hipGetLastError() == hipSuccess ? CRDT_OK : CRDT_EHIP;
 }
@@ -300,19 +296,13 @@ int launch_mvreg_merge(const uint32_t* sn, const uint64_t* sclk, const uint64_t*
   const size_t per_wave = (8ull * (scap + ocap) * A + (size_t)scap * ocap + (size_t)ocap * ocap + outcap + 15u) & ~15ull;
   if (scap > kMvBigCap || ocap > kMvBigCap) return CRDT_EINVAL;
   if (per_wave > 60u * 1024u || scap > 64u || ocap > 64u) {  // past the fast kernel's limits
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const uint64_t cap = (uint64_t)cus * 16u;
-    hipLaunchKernelGGL(mvreg_merge_big_kernel, dim3((uint32_t)(n_obj < cap ? n_obj : cap)), dim3(kMW), 0, stream, sn,
-                       sclk, sval, scap, on, oclk, oval, ocap, outn, outclk, outval, outcap, n_obj, A, status);
+    hipLaunchKernelGGL(mvreg_merge_big_kernel, dim3(resident_blocks(n_obj, 16u)), dim3(kMW), 0, stream, sn, sclk, sval,
+                       scap, on, oclk, oval, ocap, outn, outclk, outval, outcap, n_obj, A, status);
     return hipGetLastError() == hipSuccess ? CRDT_OK : CRDT_EHIP;
   }
   uint32_t W = 4;  // waves per block, as many as 60 KB of LDS allow
   while (W > 1u && W * per_wave > 60u * 1024u) --W;
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const uint64_t want = (n_obj + W - 1) / W, cap = (uint64_t)cus * (32u / W);  // ~8 waves per SIMD
-  const uint32_t blocks = (uint32_t)(want < cap ? want : cap);
+  const uint32_t blocks = resident_blocks((n_obj + W - 1) / W, 32u / W);  // ~8 waves per SIMD
   hipLaunchKernelGGL(mvreg_merge_kernel, dim3(blocks), dim3(kMW * W), W * per_wave, stream, sn, sclk, sval, scap, on,
                      oclk, oval, ocap, outn, outclk, outval, outcap, n_obj, A, (uint32_t)per_wave, status);
   return hipGetLastError() == hipSuccess ? CRDT_OK : CRDT_EHIP;

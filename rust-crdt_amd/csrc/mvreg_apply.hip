@@ -36,34 +36,17 @@
 
 #include "../../include/crdts_hip.h"
 #include "kernels.h"
+#include "sched.h"
+#include "wave.h"
 
 namespace crdts_hip {
 namespace {
 
-constexpr uint32_t kW = 64;
+using namespace wave;  // kW, sync, uni32 / uni64, lane64, shfl64, mbcnt (wave.h)
+
 constexpr uint32_t kBigCap = 2048;   // out_cap's ABI limit (api.hip)
 constexpr uint32_t kTruncCap = 1024;  // self_cap's ABI limit
 
-__device__ __forceinline__ void ra_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ uint32_t uni32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint64_t uni64(uint64_t v) {
-  return ((uint64_t)uni32((uint32_t)(v >> 32)) << 32) | uni32((uint32_t)v);
-}
-__device__ __forceinline__ uint64_t lane64(uint64_t v, uint32_t l) {  // l wave-uniform
-  return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), (int)l) << 32) |
-         (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, (int)l);
-}
-__device__ __forceinline__ uint64_t shfl64(uint64_t v, uint32_t l) {
-  return ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(v >> 32), (int)l, kW) << 32) |
-         (uint32_t)__shfl((int)(uint32_t)v, (int)l, kW);
-}
-__device__ __forceinline__ uint32_t rank_in(uint64_t m) {  // set bits of m below this lane
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
 // Does `ballot` (of elements base .. base + 63) have a bit inside the element
 // range [sA, eA)?
 __device__ __forceinline__ bool seg_any(uint64_t ballot, uint32_t base, uint32_t sA, uint32_t eA) {
@@ -140,7 +123,7 @@ __global__ __launch_bounds__(256) void mvreg_apply_kernel(
       pa = P.clk_act[pb + lane];
       pc = P.clk_ctr[pb + lane];
     }
-    ra_sync();  // the previous object's readers of the region are done
+    sync();  // the previous object's readers of the region are done
     if (lane < ns * A) Wk[lane] = cS;
     for (uint32_t e = kW + lane; e < ns * A; e += kW) Wk[e] = sclk[o * scap * A + e];
     if (lane < ns) V[lane] = cV;
@@ -166,9 +149,9 @@ __global__ __launch_bounds__(256) void mvreg_apply_kernel(
       const uint32_t np = (uint32_t)(chi - clo);
       if (np == 0u) continue;  // an empty Put clock: unchanged
       const uint64_t val = lane64(hv, t);
-      ra_sync();  // the previous op's reads of oc are done
+      sync();  // the previous op's reads of oc are done
       for (uint32_t x = lane; x < A; x += kW) oc[x] = 0ull;
-      ra_sync();
+      sync();
       bool cbad = false;
       if (chi - pb <= kW) {  // its pairs are staged, from lane clo - pb
         const uint32_t f = (uint32_t)(clo - pb);
@@ -191,7 +174,7 @@ __global__ __launch_bounds__(256) void mvreg_apply_kernel(
         err = CRDT_ENONCANON;
         break;
       }
-      ra_sync();
+      sync();
       // one compare per stored element; slot `lane` collects its segment's flags
       bool gt = false, lt = false;
       {
@@ -247,8 +230,8 @@ __global__ __launch_bounds__(256) void mvreg_apply_kernel(
       continue;
     }
     const uint32_t nk = (uint32_t)__popcll(used);
-    if (lane < hw && ((used >> lane) & 1ull)) tab[rank_in(used)] = (uint8_t)lane;
-    ra_sync();
+    if (lane < hw && ((used >> lane) & 1ull)) tab[mbcnt(used)] = (uint8_t)lane;
+    sync();
     if (lane == 0u) outn[o] = nk;
     if (lane < outcap) outval[o * outcap + lane] = lane < nk ? V[tab[lane]] : 0ull;
     uint64_t* od = outclk + o * (uint64_t)AO;
@@ -267,7 +250,7 @@ __global__ __launch_bounds__(256) void mvreg_apply_kernel(
 // returns their count. Every row moves with the same lane <-> actor mapping.
 __device__ uint32_t big_compact(uint64_t* W, uint64_t* V, uint32_t* nnz_s, uint8_t* used_s, uint32_t hw, uint32_t A,
                                 uint32_t lane) {
-  ra_sync();
+  sync();
   uint32_t dst = 0u;
   for (uint32_t s = 0; s < hw; ++s) {
     if (!uni32(used_s[s])) continue;
@@ -280,9 +263,9 @@ __device__ uint32_t big_compact(uint64_t* W, uint64_t* V, uint32_t* nnz_s, uint8
     }
     ++dst;
   }
-  ra_sync();
+  sync();
   for (uint32_t k = lane; k < hw; k += kW) used_s[k] = k < dst ? 1u : 0u;
-  ra_sync();
+  sync();
   return dst;
 }
 
@@ -304,7 +287,7 @@ __global__ __launch_bounds__(kW) void mvreg_apply_big_kernel(
     uint64_t* W = outclk + o * (uint64_t)outcap * A;
     uint64_t* V = outval + o * (uint64_t)outcap;
     const uint64_t* S = sclk + o * (uint64_t)scap * A;
-    ra_sync();  // the previous object's readers of nnz_s / used_s are done
+    sync();  // the previous object's readers of nnz_s / used_s are done
     for (uint32_t k = 0; k < ns; ++k) {
       uint32_t cnt = 0u;
       for (uint32_t x0 = 0; x0 < A; x0 += kW) {
@@ -325,7 +308,7 @@ __global__ __launch_bounds__(kW) void mvreg_apply_big_kernel(
     uint32_t hw = ns, cnt = ns;
     int err = 0;
     uint64_t clo = lo ? uni64(P.clk_end[lo - 1u]) : 0ull;
-    ra_sync();
+    sync();
     for (uint64_t j = lo; j < hi; ++j) {
       const uint64_t chi = uni64(P.clk_end[j]);
       if (clo > chi || chi > nclk || chi - clo > A) {
@@ -376,9 +359,9 @@ __global__ __launch_bounds__(kW) void mvreg_apply_big_kernel(
       cnt = nk;
       if (anydom) continue;
       if (hw == outcap) hw = big_compact(W, V, nnz_s, used_s, hw, A, lane);
-      ra_sync();
+      sync();
       for (uint32_t x = lane; x < A; x += kW) W[(uint64_t)hw * A + x] = 0ull;
-      ra_sync();
+      sync();
       for (uint32_t p = lane; p < np; p += kW) W[(uint64_t)hw * A + P.clk_act[c0 + p]] = P.clk_ctr[c0 + p];
       if (lane == 0u) {
         V[hw] = P.val[j];
@@ -387,7 +370,7 @@ __global__ __launch_bounds__(kW) void mvreg_apply_big_kernel(
       }
       ++hw;
       ++cnt;
-      ra_sync();
+      sync();
     }
     if (err) {
       if (lane == 0u) atomicCAS(status, 0, err);
@@ -422,7 +405,7 @@ __global__ __launch_bounds__(256) void mvreg_truncate_kernel(
     }
     const uint64_t* S = sclk + o * (uint64_t)scap * A;
     const uint64_t* T = clock + o * (uint64_t)A;
-    ra_sync();  // the previous object's readers of tab are done
+    sync();  // the previous object's readers of tab are done
     uint32_t nk = 0u;
     if (ns <= kW && A <= 65536u) {  // lane = element; slot `lane` collects its segment's ballot bits
       bool keep = false;
@@ -438,7 +421,7 @@ __global__ __launch_bounds__(256) void mvreg_truncate_kernel(
       }
       keep = keep && lane < ns;
       const uint64_t m = __ballot(keep);
-      if (keep) tab[rank_in(m)] = (uint16_t)lane;
+      if (keep) tab[mbcnt(m)] = (uint16_t)lane;
       nk = (uint32_t)__popcll(m);
     } else {  // lane = slot
       for (uint32_t b = 0; b < ns; b += kW) {
@@ -447,11 +430,11 @@ __global__ __launch_bounds__(256) void mvreg_truncate_kernel(
         if (k < ns)
           for (uint32_t x = 0; x < A && !keep; ++x) keep = S[(uint64_t)k * A + x] > T[x];
         const uint64_t m = __ballot(keep);
-        if (keep) tab[nk + rank_in(m)] = (uint16_t)k;
+        if (keep) tab[nk + mbcnt(m)] = (uint16_t)k;
         nk += (uint32_t)__popcll(m);
       }
     }
-    ra_sync();
+    sync();
     if (lane == 0u) outn[o] = nk;
     for (uint32_t k = lane; k < outcap; k += kW) outval[o * outcap + k] = k < nk ? sval[o * scap + tab[k]] : 0ull;
     uint64_t* od = outclk + o * AO;
@@ -495,12 +478,6 @@ __global__ __launch_bounds__(256) void mvreg_read_clock_kernel(const uint32_t* _
   }
 }
 
-int n_cus() {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  return cus;
-}
-
 }  // namespace
 
 int launch_mvreg_apply(const uint32_t* sn, const uint64_t* sclk, const uint64_t* sval, uint32_t scap,
@@ -508,7 +485,7 @@ int launch_mvreg_apply(const uint32_t* sn, const uint64_t* sclk, const uint64_t*
                        uint64_t n_obj, uint32_t A, int* status, hipStream_t stream) {
   if (n_obj == 0) return CRDT_OK;
   if (outcap > kBigCap || scap > outcap) return CRDT_EINVAL;
-  const uint64_t cus = (uint64_t)n_cus();
+  const uint64_t cus = (uint64_t)cu_count();
   // per-wave LDS: the block, the op row, the values, the slot table; 16-B multiple
   const size_t per_wave = (8ull * ((size_t)outcap * A + A + outcap) + outcap + 15u) & ~15ull;
   if (outcap > 64u || per_wave > 60u * 1024u) {
@@ -533,7 +510,7 @@ int launch_mvreg_truncate(const uint32_t* sn, const uint64_t* sclk, const uint64
                           uint64_t n_obj, uint32_t A, int* status, hipStream_t stream) {
   if (n_obj == 0) return CRDT_OK;
   if (scap > kTruncCap || scap > outcap) return CRDT_EINVAL;
-  const uint64_t want = (n_obj + 3u) / 4u, cap = (uint64_t)n_cus() * 8u;  // 8 waves per SIMD
+  const uint64_t want = (n_obj + 3u) / 4u, cap = (uint64_t)cu_count() * 8u;  // 8 waves per SIMD
   hipLaunchKernelGGL(mvreg_truncate_kernel, dim3((uint32_t)(want < cap ? want : cap)), dim3(256), 0, stream, sn, sclk,
                      sval, scap, clock, outn, outclk, outval, outcap, n_obj, A, status);
   return hipGetLastError() == hipSuccess ? CRDT_OK : CRDT_EHIP;
@@ -542,7 +519,7 @@ int launch_mvreg_truncate(const uint32_t* sn, const uint64_t* sclk, const uint64
 int launch_mvreg_read_clock(const uint32_t* sn, const uint64_t* sclk, uint32_t scap, uint64_t* out, uint64_t n_obj,
                             uint32_t A, int* status, hipStream_t stream) {
   if (n_obj == 0) return CRDT_OK;
-  const uint64_t want = (n_obj * A + 255u) / 256u, cap = (uint64_t)n_cus() * 8u;
+  const uint64_t want = (n_obj * A + 255u) / 256u, cap = (uint64_t)cu_count() * 8u;
   hipLaunchKernelGGL(mvreg_read_clock_kernel, dim3((uint32_t)(want < cap ? want : cap)), dim3(256), 0, stream, sn,
                      sclk, scap, out, n_obj, A, status);
   return hipGetLastError() == hipSuccess ? CRDT_OK : CRDT_EHIP;

@@ -56,18 +56,15 @@ namespace {
 
 using namespace csr_rank;
 
-constexpr uint32_t kW = 64;
 constexpr uint32_t kBlock = 256;
 // lane tier / wave tier boundary: runs of more words (or dense slots) than
 // this are counted and copied by the wave
 constexpr uint32_t kLaneRun = 16;
 
-__device__ __forceinline__ void fail(int* status, int code) { atomicCAS(status, 0, code); }
 
 // a resident grid: 8 blocks of 4 waves per CU of the current device (sched.h)
 uint32_t chunk_blocks(uint64_t chunks) {
-  const uint64_t want = (chunks + kBlock / kW - 1) / (kBlock / kW), cap = (uint64_t)cu_count() * 8;
-  return (uint32_t)(want < cap ? want : cap);
+  return resident_blocks((chunks + kBlock / kW - 1) / (kBlock / kW));
 }
 
 // A clock as the kernels meet it: act == null is a dense row of n slots (slot k
@@ -280,14 +277,14 @@ __device__ __forceinline__ void resolve_counts(const Loc& L, bool has, const Wan
   while (pa) {
     const uint32_t t = (uint32_t)__builtin_ctzll(pa);
     pa &= pa - 1u;
-    const uint32_t c = count_wave((const uint64_t*)lane_u64((uint64_t)L.add.ctr, t), lane_u32(L.add.n, t), lane);
+    const uint32_t c = count_wave((const uint64_t*)lane64((uint64_t)L.add.ctr, t), lane32(L.add.n, t), lane);
     add_len = lane == t ? c : add_len;
   }
   uint64_t pr = __ballot(rm_w);
   while (pr) {
     const uint32_t t = (uint32_t)__builtin_ctzll(pr);
     pr &= pr - 1u;
-    const uint32_t c = count_wave((const uint64_t*)lane_u64((uint64_t)L.rm.ctr, t), lane_u32(L.rm.n, t), lane);
+    const uint32_t c = count_wave((const uint64_t*)lane64((uint64_t)L.rm.ctr, t), lane32(L.rm.n, t), lane);
     rm_len = lane == t ? c : rm_len;
   }
   if (has && w.add) add_len += L.grow;
@@ -416,10 +413,10 @@ __device__ __forceinline__ void emit_group(const Run& r, bool go, uint32_t wa, u
   while (pend) {
     const uint32_t t = (uint32_t)__builtin_ctzll(pend);
     pend &= pend - 1u;
-    const Run rt{(const uint64_t*)lane_u64((uint64_t)r.ctr, t), (const uint32_t*)lane_u64((uint64_t)r.act, t),
-                 lane_u32(r.n, t)};
-    const uint64_t a0 = lane_u64(at, t);
-    emit_wave(rt, lane_u32(wa, t), lane_u64(wc, t), oa, oc, a0, a0 + lane_u32(len, t), lane);
+    const Run rt{(const uint64_t*)lane64((uint64_t)r.ctr, t), (const uint32_t*)lane64((uint64_t)r.act, t),
+                 lane32(r.n, t)};
+    const uint64_t a0 = lane64(at, t);
+    emit_wave(rt, lane32(wa, t), lane64(wc, t), oa, oc, a0, a0 + lane32(len, t), lane);
   }
 }
 
@@ -434,7 +431,7 @@ __device__ __forceinline__ void close_unknown_kinds(const crdt_read_queries& Q, 
     while (m) {
       const uint32_t u = (uint32_t)__builtin_ctzll(m);
       m &= m - 1u;
-      if (lane == lane_u32(t, u)) {
+      if (lane == lane32(t, u)) {
         ok = 0u;
         bad = true;
       }
@@ -516,9 +513,9 @@ __global__ __launch_bounds__(kBlock) void read_kernel(Src S, crdt_read_queries Q
       while (pend) {
         const uint32_t u = (uint32_t)__builtin_ctzll(pend);
         pend &= pend - 1u;
-        const uint64_t* src = (const uint64_t*)lane_u64((uint64_t)L.list, u);
-        const uint32_t n = lane_u32(L.list_n, u);
-        const uint64_t a0 = lane_u64(at, u);
+        const uint64_t* src = (const uint64_t*)lane64((uint64_t)L.list, u);
+        const uint32_t n = lane32(L.list_n, u);
+        const uint64_t a0 = lane64(at, u);
         for (uint32_t k = lane; k < n; k += kW) O.list_key[a0 + k] = src[k];
       }
     });
@@ -574,8 +571,8 @@ __global__ __launch_bounds__(kBlock) void mvreg_get_kernel(MapSrc S, const uint3
       while (pend) {
         const uint32_t u = (uint32_t)__builtin_ctzll(pend);
         pend &= pend - 1u;
-        const uint64_t jr = lane_u64(j, u), rr = lane_u64(row, u);
-        const uint32_t nn = lane_u32(n, u);
+        const uint64_t jr = lane64(j, u), rr = lane64(row, u);
+        const uint32_t nn = lane32(n, u);
         const uint64_t* sc = mv_clock + rr * mcap * A;
         uint64_t* dc = out_clk + jr * out_cap * A;
         const uint64_t used = (uint64_t)nn * A, all = (uint64_t)out_cap * A;

@@ -1,4 +1,5 @@
-// Object schedule of the one-object-per-wave kernels (internal).
+// Launch sizing (cu_count, resident_blocks, coprime_grid) and the object
+// schedules of the one-object-per-wave kernels (internal).
 //
 // A resident grid with a static split leaves the youngest waves of every
 // SIMD running last: the issue arbiter favours the oldest waves, so with
@@ -21,6 +22,13 @@ inline int cu_count() {
   int dev = 0, cus = 256;
   if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   return cus;
+}
+
+// A resident grid: `want` blocks, at most per_cu to a CU (8 blocks of 4 waves
+// fill a CU's 32 wave slots).
+inline uint32_t resident_blocks(uint64_t want, uint32_t per_cu = 8) {
+  const uint64_t cap = (uint64_t)cu_count() * per_cu;
+  return (uint32_t)(want < cap ? want : cap);
 }
 
 // The largest grid <= blocks that shares no factor with `slots`: the kept keys

@@ -33,17 +33,15 @@
 #include "kernels.h"
 #include "record_layout.h"
 #include "sched.h"
+#include "wave.h"
 
 namespace crdts_hip {
 namespace {
 
-constexpr uint32_t kW = 64;
+using namespace wave;  // kW, sync, lane64, mbcnt, fail (wave.h)
+
 constexpr uint32_t kEmptyClockFlag = 2u;  // CRDT_ORSWOT_EMPTY_MEMBER_CLOCK
 
-__device__ __forceinline__ void fail(int* status, int code) { atomicCAS(status, 0, code); }
-__device__ __forceinline__ uint32_t mbcnt(uint64_t m) {
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
   for (uint32_t s = 32u; s; s >>= 1) v += __shfl_xor(v, (int)s);
   return v;
@@ -392,12 +390,6 @@ struct TWs {
   uint32_t nm[kTStage / 24];  // per member: the deferred clocks naming it (a member takes >= 24 B of a record)
 };
 
-__device__ __forceinline__ void tsync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 constexpr uint32_t kTPer = kTStage / 16u / kW;  // 16-B record pieces per lane
 typedef uint32_t tu32x4 __attribute__((ext_vector_type(4)));
 // An LDS-form object's record (every 16-B piece, clamped to its last) and the
@@ -428,7 +420,7 @@ __device__ void tstage(TWs& w, const RecLayout& L, const TPre& p, const Run& c, 
   if (lane < kTA) w.ct[lane] = 0ull;
   for (uint32_t k = lane; k < kTDef * kTA; k += kW) w.drow[k / kTA][k % kTA] = 0ull;
   for (uint32_t m = lane; m < L.n_mem; m += kW) w.nm[m] = 0u;
-  tsync();
+  sync();
   if (p.a < kTA) w.ct[p.a] = p.c;  // actors >= A name nothing a dense record holds
   for (uint32_t e = kW + lane; e < c.n; e += kW) {
     const uint32_t x = c.a[e];
@@ -448,7 +440,7 @@ __device__ void truncate_lds(const TruncArgs& g, const Rec& R, uint64_t o, uint3
     for (uint32_t d = lane; d < L.n_def_dot; d += kW) wd = wd || ((const uint32_t*)(S + L.o_fact))[d] >= A;
     if (__ballot(wd) != 0ull) {
       wide = true;
-      tsync();
+      sync();
       return;
     }
   }
@@ -481,7 +473,7 @@ __device__ void truncate_lds(const TruncArgs& g, const Rec& R, uint64_t o, uint3
     }
     if (lo < L.n_mem && key[lo] == m && k < kTDef) atomicOr(&w.nm[lo], 1u << k);
   }
-  tsync();
+  sync();
   auto mend = [&](uint32_t m) { return min(mdend[m], L.n_dot); };
   auto mbeg = [&](uint32_t m) { return m ? min(mend(m - 1u), mend(m)) : 0u; };
   auto fdb = [&](uint32_t k) { return k ? min(min(fdend[k - 1u], L.n_def_dot), min(fdend[k], L.n_def_dot)) : 0u; };
@@ -530,11 +522,11 @@ __device__ void truncate_lds(const TruncArgs& g, const Rec& R, uint64_t o, uint3
     rec_layout(O, A, n_mem, n_dot, 0u, 0u, 0u, false);
     if (O.size > L.size) {  // cannot happen for a canonical record
       if (lane == 0u) fail(g.status, CRDT_ENONCANON);
-      tsync();
+      sync();
       return;
     }
     uint8_t* wout = g.out + o;
-    tsync();  // every read of the stage is done: the output is assembled over it
+    sync();  // every read of the stage is done: the output is assembled over it
     uint8_t* S8 = (uint8_t*)w.stage;
     if (lane < A) ((uint64_t*)(S8 + O.o_clk))[lane] = tx > cx ? tx : 0ull;
     if (kept) {
@@ -559,10 +551,10 @@ __device__ void truncate_lds(const TruncArgs& g, const Rec& R, uint64_t o, uint3
       for (uint32_t t = 0; t < 8u; ++t) h = lane == t ? hv[t] : h;
       ((uint32_t*)S8)[lane] = h;
     }
-    tsync();
+    sync();
     for (uint32_t k = lane; k < O.size / 16u; k += kW)
       __builtin_nontemporal_store(((const tu32x4*)S8)[k], (tu32x4*)wout + k);
-    tsync();  // the stage is reused by the wave's next record
+    sync();  // the stage is reused by the wave's next record
     return;
   }
 
@@ -707,7 +699,7 @@ __device__ void truncate_lds(const TruncArgs& g, const Rec& R, uint64_t o, uint3
     hw[6] = n_fmem;
     hw[7] = g.flags | (empty_clock ? kEmptyClockFlag : 0u);
   }
-  tsync();  // the stage is reused by the wave's next record
+  sync();  // the stage is reused by the wave's next record
 }
 
 // One wave per 64-record chunk: lane k reads record cbase + k's offset, clock
@@ -816,7 +808,7 @@ __global__ __launch_bounds__(kW * kTWaves, 4) void orswot_truncate_kernel(TruncA
         if (wide) truncate_global(g, Rc, cc, oc, lane);
       } else {
         if (lane == 0u) fail(g.status, CRDT_ENONCANON);
-        tsync();  // the stage is reused by the wave's next record
+        sync();  // the stage is reused by the wave's next record
       }
       if (!more) break;
     }
@@ -856,11 +848,6 @@ struct TFWs {
   uint64_t drow[kTFDef][kTA];  // the deferred clocks, dense
   uint32_t names[kW];          // per member: the deferred clocks naming it
 };
-__device__ __forceinline__ void tf_sync() { tsync(); }
-__device__ __forceinline__ uint64_t lane64(uint64_t v, uint32_t t) {
-  return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)(v >> 32), t) << 32) |
-         (uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)v, t);
-}
 __device__ __forceinline__ uint64_t below_mask(uint32_t n) { return n >= 64u ? ~0ull : (1ull << n) - 1ull; }
 
 __global__ __launch_bounds__(kW * kTWaves, 8) void orswot_truncate_fast_kernel(TruncArgs g, uint32_t* ctl,
@@ -959,7 +946,7 @@ __global__ __launch_bounds__(kW * kTWaves, 8) void orswot_truncate_fast_kernel(T
       const uint32_t cnt = (uint32_t)__builtin_amdgcn_readlane(cn, t);
       // canonical run: actors strictly increasing, counters > 0
       const bool cbad = lane < cnt && (rc == 0ull || (lane > 0u && ra <= prev));
-      tf_sync();
+      sync();
       if (lane < cnt && ra < kTA) w.ct[ra] = rc;
       const uint64_t oo = lane64(o, t);
       const uint32_t md = (uint32_t)__builtin_amdgcn_readlane(nmd, t);
@@ -1006,7 +993,7 @@ __global__ __launch_bounds__(kW * kTWaves, 8) void orswot_truncate_fast_kernel(T
       const uint32_t u = more ? (uint32_t)__builtin_ctzll(pend) : t;
       pend &= pend - 1u;
       fetch(u);
-      tf_sync();
+      sync();
       // ---- members and dots
       const bool hm = lane < nM, hd = lane < nD;
       const uint64_t km = hm ? ((const uint64_t*)(S + L.o_key))[lane] : 0ull;
@@ -1071,7 +1058,7 @@ __global__ __launch_bounds__(kW * kTWaves, 8) void orswot_truncate_fast_kernel(T
         oe_d = (uint32_t)__popcll(FE & below_mask(((const uint32_t*)(S + L.o_fdend))[lane]));
         oe_m = (uint32_t)__popcll(ME & below_mask(((const uint32_t*)(S + L.o_fmend))[lane]));
       }
-      tf_sync();  // every read of the stage is done: the output is assembled over it
+      sync();  // every read of the stage is done: the output is assembled over it
       if (!bad) {
         uint8_t* W = (uint8_t*)w.stage;
         if (lane < A) ((uint64_t*)(W + kHdrBytes))[lane] = tx > cx ? tx : 0ull;
@@ -1104,7 +1091,7 @@ __global__ __launch_bounds__(kW * kTWaves, 8) void orswot_truncate_fast_kernel(T
                               : g.flags | (empty ? kEmptyClockFlag : 0u);
           ((uint32_t*)W)[lane] = hv;
         }
-        tf_sync();
+        sync();
         const uint32_t n16o = O.size / 16u;  // <= the input's pieces: at most 2 per lane
         const uint32_t i0 = lane < n16o ? lane : n16o - 1u, i1 = lane + kW < n16o ? lane + kW : n16o - 1u;
         const tu32x4 q0 = w.stage[i0], q1 = w.stage[i1];
@@ -1116,7 +1103,7 @@ __global__ __launch_bounds__(kW * kTWaves, 8) void orswot_truncate_fast_kernel(T
         if (e < list_cap) list[e] = cbase + t;
       }
       (void)iflags;
-      tf_sync();  // the copy-out's reads of the stage are done
+      sync();  // the copy-out's reads of the stage are done
       if (!more) break;
       t = u;
     }
@@ -1129,8 +1116,7 @@ int launch_orswot_truncate(const crdt_orswot_batch& self, const crdt_clock_csr& 
                            uint8_t* out, uint64_t* out_off, uint64_t out_bytes, int* status, uint32_t* ctl,
                            uint64_t* list, uint32_t list_cap, hipStream_t stream) {
   if (self.n_obj == 0) return CRDT_OK;
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  const int cus = cu_count();
   // dense batches of <= 32 actors: the fast form first (resident grid, its
   // ticket counter ctl[3] zeroed), then the general form over the records it
   // flagged; other batches: the general form over every record
