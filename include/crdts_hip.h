@@ -1696,6 +1696,113 @@ int crdt_clock_ops_to_bincode(crdt_ctx* ctx, const uint32_t* d_actor, const uint
                               const uint32_t* d_dir, size_t n_ops, uint32_t actor_bytes, uint32_t with_dir,
                               uint8_t* d_blobs, size_t stride, void* stream);
 
+/* ------------------------------------------------------------------------ *
+ * bincode of the Orswot, MVReg and Map ops (ops_bincode.hip): the wire form of
+ * the `Op` enums replicas exchange (all derive Serialize / Deserialize:
+ * src/orswot.rs:36-53, src/mvreg.rs:49-59, src/map.rs:102-123), into and out
+ * of the arrays of crdt_orswot_ops, crdt_mvreg_ops, crdt_map_mvreg_ops,
+ * crdt_map_orswot_ops and crdt_map_map_ops. One family of four calls serves
+ * the five op types, selected by op_type. obj_end is not on the wire: grouping
+ * stays the caller's, as in crdt_clock_ops_from_bincode.
+ *
+ * Wire format (bincode 0.9 of the serde derives): an enum is a little-endian
+ * u32 variant index followed by its fields in declaration order; a VClock is
+ * u64 n | n x (A actor | u64 counter), actors strictly ascending. A, K, M / K2
+ * and V are unsigned little-endian integers of actor_bytes, key_bytes,
+ * key2_bytes and val_bytes, each in {1, 2, 4, 8}; a width is read only where
+ * the op type has the field.
+ *   Orswot Op  Add: 0 | A actor | u64 counter | M member    Rm: 1 | VClock | M member   (M = key2)
+ *   MVReg  Op  Put: 0 | VClock | V val
+ *   Map    Op  Nop: 0     Rm: 1 | VClock | K key     Up: 2 | A actor | u64 counter | K key | <V::Op>
+ *     V = MVReg            <V::Op> = Put                                kind CRDT_MAP_OP_UP 2
+ *     V = Orswot           <V::Op> = Add -> kind CRDT_MAP_OP_UP 2,  Rm -> CRDT_MAP_OP_UP_RM 3
+ *     V = Map<K2, MVReg>   <V::Op> = Nop -> CRDT_MAPMAP_OP_UP_NOP 4,  Rm { clock, key2 } -> UP_RM 3,
+ *                                    Up { dot2, key2, Put } -> UP_UP 2 (actor2 / counter2 / key2 / val)
+ *   e.g. Orswot Add { dot (3, 5), member 9 } at actor_bytes 1, key2_bytes 2 is the 15 bytes
+ *     00000000 03 0500000000000000 0900; the nested Up { (1, 7), key 10, Up { (2, 3), key2 11,
+ *     Put { {1: 7}, 42 } } } at all widths 1 is the 50 bytes 02000000 01 0700000000000000 0A
+ *     02000000 02 0300000000000000 0B 00000000 0100000000000000 01 0700000000000000 2A.
+ * crdt_map_orswot_ops holds one dot per op: the nested Add's dot is the Up's,
+ * as Map::update builds it. Ingest latches CRDT_ENONCANON for a blob whose
+ * two dots differ; egest writes the dot twice. (The reference's tests assert
+ * no bytes: parity unpinned by reference output.)
+ *
+ * Op j is the blob [d_blob_off[j], d_blob_off[j] + d_blob_len[j]) of d_blobs,
+ * at any alignment. Nothing outside a blob's aligned 16-byte lines within
+ * d_blobs is read.
+ *
+ * Ingest is two calls with the caller's scan between them:
+ *   crdt_ops_bincode_clk_lens: d_clk_len[j] = the clock pairs of op j, from
+ *     its framing alone (the variant indices, the clock's length word against
+ *     the bytes left before any multiply, the exact blob length, the blob
+ *     inside d_blobs); 0 for Add, Nop and UP_NOP. A badly framed op gets 0
+ *     pairs (CRDT_OPS_MVREG: 1, for the sentinel below) and is latched.
+ *   The caller takes the inclusive prefix sum of the lens into clk_end.
+ *   crdt_ops_from_bincode: HERE out->clk_end IS AN INPUT. Every array the op
+ *     type uses is written (fields an op's kind does not carry: 0) and op j's
+ *     pairs at [clk_end[j-1], clk_end[j]). A span that is not the op's length
+ *     or that leaves [0, n_clk) latches CRDT_ECAPACITY for that op.
+ *   A bad op is latched per op, the other ops unaffected: it comes out as kind
+ *     CRDT_OP_KIND_BAD with every other field 0 (every apply rejects an
+ *     unknown kind with CRDT_ENONCANON); CRDT_OPS_MVREG has no kind array:
+ *     there the first pair of the op's span, if it has one, is (0xFFFFFFFF,
+ *     0), which crdt_mvreg_apply rejects. The other pairs of a bad op's span
+ *     are unspecified. d_op_err[j], when given, is 0 or the op's CRDT_E* code.
+ *   CRDT_ENONCANON on ingest: a blob that ends early, has trailing bytes or is
+ *     shorter than its variant word; a variant index above the type's last,
+ *     outer or inner (all four bytes are compared); a length word larger than
+ *     the bytes left can hold; clock actors not strictly ascending; a zero
+ *     counter in a clock; an actor >= 2^32 in a clock or in a dot; the
+ *     Map<Orswot> dot mismatch; a blob not inside d_blobs (off + len wrapping
+ *     included). A dot with counter 0 is accepted (the applies treat it as a
+ *     duplicate); actor ranges are the applies' to check; clocks of any length.
+ * Egest: crdt_ops_bincode_sizes, the caller's placement at any byte offsets,
+ *   crdt_ops_to_bincode. Per op CRDT_ENONCANON (size 0, nothing written): an
+ *   unknown kind; a key, member, value or actor that does not fit its width;
+ *   an op clock that is not canonical; pairs owned by a kind that carries no
+ *   clock (the wire cannot say it); clk_end decreasing or past n_clk. A blob
+ *   placed past out_bytes latches CRDT_ECAPACITY and is not written. No byte
+ *   outside the blobs is written.
+ * CRDT_EINVAL (before any device work): a null ctx, widths or arrays struct;
+ * op_type > 4; a used width outside {1, 2, 4, 8}; a null array the type uses
+ * (or a null d_blobs / d_blob_off / d_blob_len / d_clk_len / d_sizes / d_out /
+ * d_out_off) with n_ops > 0; a null pair array with n_clk > 0; an output
+ * array equal to an input array. n_ops == 0 is CRDT_OK and launches nothing.
+ * ------------------------------------------------------------------------ */
+#define CRDT_OPS_ORSWOT 0u     /* arrays of crdt_orswot_ops     */
+#define CRDT_OPS_MVREG 1u      /* arrays of crdt_mvreg_ops      */
+#define CRDT_OPS_MAP_MVREG 2u  /* arrays of crdt_map_mvreg_ops  */
+#define CRDT_OPS_MAP_ORSWOT 3u /* arrays of crdt_map_orswot_ops */
+#define CRDT_OPS_MAP_MAP 4u    /* arrays of crdt_map_map_ops    */
+#define CRDT_OP_KIND_BAD 0xFFFFFFFFu
+typedef struct crdt_op_widths {
+  uint32_t actor_bytes, key_bytes, key2_bytes, val_bytes;
+} crdt_op_widths;
+typedef struct crdt_op_arrays { /* device; n_ops long unless said; null where the op type has no such field */
+  uint32_t* kind;     /* all but MVREG */
+  uint64_t* key;      /* the three Map types: the (outer) key */
+  uint32_t* actor;    /* the (outer) dot: all but MVREG */
+  uint64_t* counter;
+  uint64_t* key2;     /* ORSWOT, MAP_ORSWOT: member; MAP_MAP: the inner key */
+  uint32_t* actor2;   /* MAP_MAP: the inner dot */
+  uint64_t* counter2;
+  uint64_t* val;      /* MVREG, MAP_MVREG, MAP_MAP: the Put's value */
+  uint64_t* clk_end;  /* n_ops; AN INPUT of crdt_ops_from_bincode */
+  uint32_t* clk_act;  /* n_clk */
+  uint64_t* clk_ctr;  /* n_clk */
+  size_t n_ops, n_clk;
+} crdt_op_arrays;
+int crdt_ops_bincode_clk_lens(crdt_ctx* ctx, const uint8_t* d_blobs, size_t blob_bytes, const uint64_t* d_blob_off,
+                              const uint64_t* d_blob_len, size_t n_ops, uint32_t op_type, const crdt_op_widths* widths,
+                              uint32_t* d_clk_len, void* stream);
+int crdt_ops_from_bincode(crdt_ctx* ctx, const uint8_t* d_blobs, size_t blob_bytes, const uint64_t* d_blob_off,
+                          const uint64_t* d_blob_len, uint32_t op_type, const crdt_op_widths* widths,
+                          const crdt_op_arrays* out, uint32_t* d_op_err, void* stream);
+int crdt_ops_bincode_sizes(crdt_ctx* ctx, uint32_t op_type, const crdt_op_widths* widths, const crdt_op_arrays* ops,
+                           uint64_t* d_sizes, void* stream);
+int crdt_ops_to_bincode(crdt_ctx* ctx, uint32_t op_type, const crdt_op_widths* widths, const crdt_op_arrays* ops,
+                        uint8_t* d_out, const uint64_t* d_out_off, size_t out_bytes, void* stream);
+
 /* Dense synthetic counters: u64[n_obj][n_actors] rows for objects
  * [first_obj, first_obj+n_obj), counter U[0, 2^bits) with `pct_zero` % zeros. */
 int crdt_dense_generate(uint64_t seed, size_t first_obj, size_t n_obj, uint32_t n_actors,

@@ -20,6 +20,7 @@ import numpy as np
 from ._lib import (CRDT_COMM_ID_BYTES, CRDT_ECAPACITY, CRDT_EINVAL, CRDT_ENONCANON, CRDT_OK, EXPORTS, LIB_PATH, SPARSE_CLOCK, Batch, CrdtError,
                    GenParams, RepParams, check, lib)
 from .clock_bincode import ClockBincodeEngine
+from .ops_bincode import OpsBincodeEngine
 from .lwwreg import (LWWREG_MAX_REPS, LWWREG_WAVE_MIN_OPS, ConflictingMarker, LWWBatch, LWWEngine, LWWOps, LWWReg)
 from .record import decode_record, encode_record, record_bytes
 
@@ -214,6 +215,27 @@ class OrswotOps:
 
         return cls(u64(ends), u32(kind), u64(mem), u32(act), u64(ctr), u64(cend), u32(cact), u64(cctr))
 
+    @classmethod
+    def from_bincode(cls, blobs, blob_off, blob_len, obj_end, actor_bytes, member_bytes, engine=None,
+                     stream=None, check_status=True):
+        """Orswot Op<M, A> blobs (src/orswot.rs:36-53) as they travel between
+        replicas — blob j is blobs[blob_off[j] : blob_off[j] + blob_len[j]] (uint8
+        / int64 device tensors) — -> an op batch (crdt_ops_from_bincode). obj_end (int64
+        device tensor, or a host array) groups them: grouping is not on the
+        wire. A malformed op gets the kind every apply rejects
+        (CRDT_ENONCANON here too)."""
+        from .ops_bincode import ops_from_wire
+
+        w = (actor_bytes, 0, member_bytes, 0)
+        return ops_from_wire(cls, blobs, blob_off, blob_len, obj_end, w, engine, stream, check_status)
+
+    def to_bincode(self, actor_bytes, member_bytes, engine=None, stream=None, check_status=True):
+        """The ops' wire form -> (blobs uint8, blob_off int64, blob_len int64),
+        packed back to back (crdt_ops_to_bincode)."""
+        from .ops_bincode import ops_to_wire
+
+        return ops_to_wire(self, (actor_bytes, 0, member_bytes, 0), engine, stream, check_status)
+
 
 class MapOps:
     """A batch of Map<u64, MVReg<u64, A>, A> ops (Op::Nop / Op::Rm / Op::Up
@@ -278,6 +300,27 @@ class MapOps:
         """per_obj[i] = [("up", actor, counter, key, [(a, c), ...], val) | ("rm", key, [(a, c), ...]) | ("nop",), ...]"""
         return cls.from_arrays(*cls.arrays_from_lists(per_obj), device=device)
 
+    @classmethod
+    def from_bincode(cls, blobs, blob_off, blob_len, obj_end, actor_bytes, key_bytes, val_bytes, engine=None,
+                     stream=None, check_status=True):
+        """Map<K, MVReg> Op blobs (src/map.rs:102-123) as they travel between
+        replicas — blob j is blobs[blob_off[j] : blob_off[j] + blob_len[j]] (uint8
+        / int64 device tensors) — -> an op batch (crdt_ops_from_bincode). obj_end (int64
+        device tensor, or a host array) groups them: grouping is not on the
+        wire. A malformed op gets the kind every apply rejects
+        (CRDT_ENONCANON here too)."""
+        from .ops_bincode import ops_from_wire
+
+        w = (actor_bytes, key_bytes, 0, val_bytes)
+        return ops_from_wire(cls, blobs, blob_off, blob_len, obj_end, w, engine, stream, check_status)
+
+    def to_bincode(self, actor_bytes, key_bytes, val_bytes, engine=None, stream=None, check_status=True):
+        """The ops' wire form -> (blobs uint8, blob_off int64, blob_len int64),
+        packed back to back (crdt_ops_to_bincode)."""
+        from .ops_bincode import ops_to_wire
+
+        return ops_to_wire(self, (actor_bytes, key_bytes, 0, val_bytes), engine, stream, check_status)
+
 
 class MVRegOps:
     """A batch of MVReg<u64, A> ops (Op::Put { clock, val }, src/mvreg.rs:51-59)
@@ -338,6 +381,27 @@ class MVRegOps:
     def from_lists(cls, per_obj, device=0):
         """per_obj[i] = [(clock_pairs, val), ...]"""
         return cls.from_arrays(*cls.arrays_from_lists(per_obj), device=device)
+
+    @classmethod
+    def from_bincode(cls, blobs, blob_off, blob_len, obj_end, actor_bytes, val_bytes, engine=None,
+                     stream=None, check_status=True):
+        """MVReg Op<V, A> blobs (src/mvreg.rs:49-59) as they travel between
+        replicas — blob j is blobs[blob_off[j] : blob_off[j] + blob_len[j]] (uint8
+        / int64 device tensors) — -> an op batch (crdt_ops_from_bincode). obj_end (int64
+        device tensor, or a host array) groups them: grouping is not on the
+        wire. A malformed op gets the kind every apply rejects
+        (CRDT_ENONCANON here too)."""
+        from .ops_bincode import ops_from_wire
+
+        w = (actor_bytes, 0, 0, val_bytes)
+        return ops_from_wire(cls, blobs, blob_off, blob_len, obj_end, w, engine, stream, check_status)
+
+    def to_bincode(self, actor_bytes, val_bytes, engine=None, stream=None, check_status=True):
+        """The ops' wire form -> (blobs uint8, blob_off int64, blob_len int64),
+        packed back to back (crdt_ops_to_bincode)."""
+        from .ops_bincode import ops_to_wire
+
+        return ops_to_wire(self, (actor_bytes, 0, 0, val_bytes), engine, stream, check_status)
 
 
 class ClockOps:
@@ -585,6 +649,28 @@ class MapMapOps:
         """per_obj[i] = the object's ops in their JSON form, as for arrays_from_lists."""
         return cls.from_arrays(*cls.arrays_from_lists(per_obj), device=device)
 
+    @classmethod
+    def from_bincode(cls, blobs, blob_off, blob_len, obj_end, actor_bytes, key_bytes, inner_key_bytes, val_bytes,
+                     engine=None, stream=None, check_status=True):
+        """Map<K, Map<K2, MVReg>> Op blobs (src/map.rs:102-123) as they travel between
+        replicas — blob j is blobs[blob_off[j] : blob_off[j] + blob_len[j]] (uint8
+        / int64 device tensors) — -> an op batch (crdt_ops_from_bincode). obj_end (int64
+        device tensor, or a host array) groups them: grouping is not on the
+        wire. A malformed op gets the kind every apply rejects
+        (CRDT_ENONCANON here too)."""
+        from .ops_bincode import ops_from_wire
+
+        w = (actor_bytes, key_bytes, inner_key_bytes, val_bytes)
+        return ops_from_wire(cls, blobs, blob_off, blob_len, obj_end, w, engine, stream, check_status)
+
+    def to_bincode(self, actor_bytes, key_bytes, inner_key_bytes, val_bytes, engine=None, stream=None,
+                   check_status=True):
+        """The ops' wire form -> (blobs uint8, blob_off int64, blob_len int64),
+        packed back to back (crdt_ops_to_bincode)."""
+        from .ops_bincode import ops_to_wire
+
+        return ops_to_wire(self, (actor_bytes, key_bytes, inner_key_bytes, val_bytes), engine, stream, check_status)
+
 
 class MapOrswotOps:
     """A batch of Map<u64, Orswot<u64, A>, A> ops (Op::Nop / Op::Rm / Op::Up
@@ -650,6 +736,27 @@ class MapOrswotOps:
     def from_lists(cls, per_obj, device=0):
         """per_obj[i] = the object's op tuples, as for arrays_from_lists."""
         return cls.from_arrays(*cls.arrays_from_lists(per_obj), device=device)
+
+    @classmethod
+    def from_bincode(cls, blobs, blob_off, blob_len, obj_end, actor_bytes, key_bytes, member_bytes, engine=None,
+                     stream=None, check_status=True):
+        """Map<K, Orswot> Op blobs (src/map.rs:102-123; the nested Add's dot is the Up's) as they travel between
+        replicas — blob j is blobs[blob_off[j] : blob_off[j] + blob_len[j]] (uint8
+        / int64 device tensors) — -> an op batch (crdt_ops_from_bincode). obj_end (int64
+        device tensor, or a host array) groups them: grouping is not on the
+        wire. A malformed op gets the kind every apply rejects
+        (CRDT_ENONCANON here too)."""
+        from .ops_bincode import ops_from_wire
+
+        w = (actor_bytes, key_bytes, member_bytes, 0)
+        return ops_from_wire(cls, blobs, blob_off, blob_len, obj_end, w, engine, stream, check_status)
+
+    def to_bincode(self, actor_bytes, key_bytes, member_bytes, engine=None, stream=None, check_status=True):
+        """The ops' wire form -> (blobs uint8, blob_off int64, blob_len int64),
+        packed back to back (crdt_ops_to_bincode)."""
+        from .ops_bincode import ops_to_wire
+
+        return ops_to_wire(self, (actor_bytes, key_bytes, member_bytes, 0), engine, stream, check_status)
 
 
 class MapSlab:
@@ -916,9 +1023,10 @@ class MapOrswotSlab:
         return _read_view(self.a, self.caps["kcap"])
 
 
-class Engine(LWWEngine, ClockBincodeEngine):
+class Engine(LWWEngine, ClockBincodeEngine, OpsBincodeEngine):
     """One crdt_ctx bound to a device. All merges run on the GPU (the LWWReg
-    calls live in lwwreg.py)."""
+    calls live in lwwreg.py, the clock and op-stream codecs in clock_bincode.py
+    and ops_bincode.py)."""
 
     def __init__(self, device=0):
         torch = _torch()

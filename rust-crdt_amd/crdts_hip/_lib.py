@@ -96,6 +96,7 @@ EXPORTS = [
     "crdt_clock_dense_from_bincode", "crdt_clock_dense_bincode_sizes", "crdt_clock_dense_to_bincode",
     "crdt_clock_csr_bincode_lens", "crdt_clock_csr_from_bincode", "crdt_clock_csr_bincode_sizes",
     "crdt_clock_csr_to_bincode", "crdt_clock_ops_from_bincode", "crdt_clock_ops_to_bincode",
+    "crdt_ops_bincode_clk_lens", "crdt_ops_from_bincode", "crdt_ops_bincode_sizes", "crdt_ops_to_bincode",
 ]
 
 CRDT_COMM_ID_BYTES = 128
@@ -226,6 +227,20 @@ class ClockCsrOut(C.Structure):
     """crdt_clock_csr_out (include/crdts_hip.h)."""
     _fields_ = [("off", C.c_void_p), ("len", C.c_void_p), ("act", C.c_void_p), ("ctr", C.c_void_p),
                 ("n_entries", C.c_size_t)]
+
+
+class OpWidthsC(C.Structure):
+    """crdt_op_widths (include/crdts_hip.h)."""
+    _fields_ = [(f, C.c_uint32) for f in ("actor_bytes", "key_bytes", "key2_bytes", "val_bytes")]
+
+
+OP_ARRAYS_FIELDS = ("kind", "key", "actor", "counter", "key2", "actor2", "counter2", "val", "clk_end", "clk_act",
+                    "clk_ctr")
+
+
+class OpArraysC(C.Structure):
+    """crdt_op_arrays (include/crdts_hip.h)."""
+    _fields_ = [(f, C.c_void_p) for f in OP_ARRAYS_FIELDS] + [("n_ops", C.c_size_t), ("n_clk", C.c_size_t)]
 
 
 class Xfer(C.Structure):
@@ -388,6 +403,10 @@ def _load():
         "crdt_clock_csr_to_bincode": (I, [P, C.POINTER(ClockCsr), C.POINTER(ClockCsr), U32, P, P, SZ, P]),
         "crdt_clock_ops_from_bincode": (I, [P, P, SZ, SZ, U32, U32, P, P, P, P]),
         "crdt_clock_ops_to_bincode": (I, [P, P, P, P, SZ, U32, U32, P, SZ, P]),
+        "crdt_ops_bincode_clk_lens": (I, [P, P, SZ, P, P, SZ, U32, C.POINTER(OpWidthsC), P, P]),
+        "crdt_ops_from_bincode": (I, [P, P, SZ, P, P, U32, C.POINTER(OpWidthsC), C.POINTER(OpArraysC), P, P]),
+        "crdt_ops_bincode_sizes": (I, [P, U32, C.POINTER(OpWidthsC), C.POINTER(OpArraysC), P, P]),
+        "crdt_ops_to_bincode": (I, [P, U32, C.POINTER(OpWidthsC), C.POINTER(OpArraysC), P, P, SZ, P]),
         "crdt_orswot_generate_replicas_subset": (I, [U64, SZ, SZ, C.POINTER(RepParams), U32, U32, U32, U32, I,
                                                      C.POINTER(P)]),
         "crdt_orswot_replica_join_transport": (I, [P, C.POINTER(TransportC), BP, U32, U32, P, P, SZ, C.POINTER(SZ),

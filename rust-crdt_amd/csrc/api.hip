@@ -1260,4 +1260,121 @@ int crdt_map_mvreg_get(crdt_ctx* ctx, const crdt_map_mvreg_slab* slab, const crd
                               ctx->d_status, S(stream));
 }
 
+// ------------------------------------------------------------------------
+// bincode of the Orswot, MVReg and Map ops (ops_bincode.hip)
+namespace {
+// What an op type uses: the four widths and the eight per-op field arrays, in
+// the order of crdt_op_widths / crdt_op_arrays (clk_end and the pair arrays
+// are every type's).
+struct OpUse {
+  bool width[4];  // actor, key, key2, val
+  bool field[8];  // kind, key, actor, counter, key2, actor2, counter2, val
+};
+OpUse op_use(uint32_t op_type) {
+  switch (op_type) {
+    case CRDT_OPS_ORSWOT: return {{true, false, true, false}, {true, false, true, true, true, false, false, false}};
+    case CRDT_OPS_MVREG: return {{true, false, false, true}, {false, false, false, false, false, false, false, true}};
+    case CRDT_OPS_MAP_MVREG: return {{true, true, false, true}, {true, true, true, true, false, false, false, true}};
+    case CRDT_OPS_MAP_ORSWOT: return {{true, true, true, false}, {true, true, true, true, true, false, false, false}};
+    default: return {{true, true, true, true}, {true, true, true, true, true, true, true, true}};
+  }
+}
+bool op_width_ok(uint32_t w) { return w == 1u || w == 2u || w == 4u || w == 8u; }
+// The widths the kernels take: the used ones checked, the others 8 (any value
+// fits, nothing is read at them).
+bool op_widths(uint32_t op_type, const crdt_op_widths* w, crdt_op_widths* norm) {
+  if (!w || op_type > CRDT_OPS_MAP_MAP) return false;
+  const OpUse u = op_use(op_type);
+  const uint32_t in[4] = {w->actor_bytes, w->key_bytes, w->key2_bytes, w->val_bytes};
+  uint32_t out[4];
+  for (int k = 0; k < 4; ++k) {
+    if (u.width[k] && !op_width_ok(in[k])) return false;
+    out[k] = u.width[k] ? in[k] : 8u;
+  }
+  *norm = {out[0], out[1], out[2], out[3]};
+  return true;
+}
+// The arrays the type uses are there (n_ops > 0), none of them (clk_end only
+// with `with_end`: it is an input of the ingest) equals one of `others`.
+bool op_arrays_ok(uint32_t op_type, const crdt_op_arrays* a, bool with_end, std::initializer_list<const void*> others) {
+  const OpUse u = op_use(op_type);
+  const void* f[8] = {a->kind, a->key, a->actor, a->counter, a->key2, a->actor2, a->counter2, a->val};
+  std::vector<const void*> mine;
+  for (int k = 0; k < 8; ++k)
+    if (u.field[k]) mine.push_back(f[k]);
+  if (!a->clk_end) return false;
+  if (with_end) mine.push_back(a->clk_end);
+  if (a->n_clk) {
+    mine.push_back(a->clk_act);
+    mine.push_back(a->clk_ctr);
+  }
+  for (const void* m : mine) {
+    if (!m) return false;
+    for (const void* o : others)
+      if (o && o == m) return false;
+  }
+  return true;
+}
+}  // namespace
+
+int crdt_ops_bincode_clk_lens(crdt_ctx* ctx, const uint8_t* d_blobs, size_t blob_bytes, const uint64_t* d_blob_off,
+                              const uint64_t* d_blob_len, size_t n_ops, uint32_t op_type, const crdt_op_widths* widths,
+                              uint32_t* d_clk_len, void* stream) {
+  crdt_op_widths W;
+  if (!ctx || !op_widths(op_type, widths, &W)) return CRDT_EINVAL;
+  if (n_ops && (!d_blobs || !d_blob_off || !d_blob_len || !d_clk_len)) return CRDT_EINVAL;
+  if (n_ops && ((const void*)d_clk_len == d_blobs || (const void*)d_clk_len == d_blob_off ||
+                (const void*)d_clk_len == d_blob_len))
+    return CRDT_EINVAL;
+  if (n_ops == 0) return CRDT_OK;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_ops_bincode_clk_lens(d_blobs, blob_bytes, d_blob_off, d_blob_len, n_ops, op_type, W, d_clk_len,
+                                     ctx->d_status, S(stream));
+}
+
+int crdt_ops_from_bincode(crdt_ctx* ctx, const uint8_t* d_blobs, size_t blob_bytes, const uint64_t* d_blob_off,
+                          const uint64_t* d_blob_len, uint32_t op_type, const crdt_op_widths* widths,
+                          const crdt_op_arrays* out, uint32_t* d_op_err, void* stream) {
+  crdt_op_widths W;
+  if (!ctx || !out || !op_widths(op_type, widths, &W)) return CRDT_EINVAL;
+  if (out->n_ops && (!d_blobs || !d_blob_off || !d_blob_len)) return CRDT_EINVAL;
+  // clk_end is an input here: no output may be it, or a blob array
+  if (out->n_ops && !op_arrays_ok(op_type, out, false, {d_blobs, d_blob_off, d_blob_len, out->clk_end}))
+    return CRDT_EINVAL;
+  if (out->n_ops && d_op_err)
+    for (const void* r : {(const void*)d_blobs, (const void*)d_blob_off, (const void*)d_blob_len,
+                          (const void*)out->clk_end})
+      if (r == d_op_err) return CRDT_EINVAL;
+  if (out->n_ops == 0) return CRDT_OK;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_ops_from_bincode(d_blobs, blob_bytes, d_blob_off, d_blob_len, op_type, W, *out, d_op_err,
+                                 ctx->d_status, S(stream));
+}
+
+int crdt_ops_bincode_sizes(crdt_ctx* ctx, uint32_t op_type, const crdt_op_widths* widths, const crdt_op_arrays* ops,
+                           uint64_t* d_sizes, void* stream) {
+  crdt_op_widths W;
+  if (!ctx || !ops || !op_widths(op_type, widths, &W)) return CRDT_EINVAL;
+  if (ops->n_ops && (!d_sizes || !op_arrays_ok(op_type, ops, true, {d_sizes}))) return CRDT_EINVAL;
+  if (ops->n_ops == 0) return CRDT_OK;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_ops_to_bincode(op_type, W, *ops, d_sizes, nullptr, nullptr, 0, ctx->d_status, S(stream));
+}
+
+int crdt_ops_to_bincode(crdt_ctx* ctx, uint32_t op_type, const crdt_op_widths* widths, const crdt_op_arrays* ops,
+                        uint8_t* d_out, const uint64_t* d_out_off, size_t out_bytes, void* stream) {
+  crdt_op_widths W;
+  if (!ctx || !ops || !op_widths(op_type, widths, &W)) return CRDT_EINVAL;
+  if (ops->n_ops && (!d_out || !d_out_off || (const void*)d_out == d_out_off ||
+                     !op_arrays_ok(op_type, ops, true, {d_out})))
+    return CRDT_EINVAL;
+  if (ops->n_ops == 0) return CRDT_OK;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_ops_to_bincode(op_type, W, *ops, nullptr, d_out, d_out_off, out_bytes, ctx->d_status, S(stream));
+}
+
 }  // extern "C"

@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/crdts_hip.h"
+#include "blob.h"
 #include "csr_rank.h"
 #include "ctx.h"
 #include "kernels.h"
@@ -37,77 +38,13 @@
 namespace crdts_hip {
 namespace {
 
+using namespace blob;
 using namespace csr_rank;
 
 constexpr uint32_t kBlock = 256;
 constexpr uint32_t kTile = 1024;  // u64 words of LDS per wave (dense ingest)
 
-
-// ------------------------------------------------------------- byte fields
-// [lo, hi): the bytes that may be read (d_blobs)
-struct Bounds {
-  uintptr_t lo, hi;
-};
-
-template <uint32_t W>
-__device__ __forceinline__ uint64_t rd_le(const uint8_t* p, const Bounds& s) {
-  const uint32_t r = (uint32_t)((uintptr_t)p & 7u);
-  const uintptr_t w0 = (uintptr_t)p - r;
-  const bool two = r + W > 8u;
-  if (w0 >= s.lo && w0 + (two ? 16u : 8u) <= s.hi) {
-    uint64_t v = *(const uint64_t*)w0 >> (8u * r);
-    if (two) v |= *(const uint64_t*)(w0 + 8u) << (64u - 8u * r);  // two: r > 0
-    return W == 8u ? v : v & ((1ull << (8u * (W & 7u))) - 1ull);
-  }
-  uint64_t v = 0;
-  for (uint32_t k = 0; k < W; ++k) v |= (uint64_t)p[k] << (8u * k);
-  return v;
-}
-
-// A field stored in aligned pieces, without a loop: up to the next 8-byte
-// boundary in rising sizes (1, 2, 4), past it in falling sizes (4, 2, 1).
-template <uint32_t W>
-__device__ __forceinline__ void wr_le(uint8_t* p, uint64_t v) {
-  const uint32_t r = (uint32_t)((uintptr_t)p & 7u);
-  if (W == 1u) {
-    *p = (uint8_t)v;
-  } else if (W == 2u) {
-    if (r & 1u) {
-      p[0] = (uint8_t)v;
-      p[1] = (uint8_t)(v >> 8);
-    } else {
-      *(uint16_t*)p = (uint16_t)v;
-    }
-  } else if (W == 4u) {
-    if ((r & 3u) == 0u) {
-      *(uint32_t*)p = (uint32_t)v;
-    } else if ((r & 1u) == 0u) {
-      *(uint16_t*)p = (uint16_t)v;
-      *(uint16_t*)(p + 2) = (uint16_t)(v >> 16);
-    } else {
-      p[0] = (uint8_t)v;
-      *(uint16_t*)(p + 1) = (uint16_t)(v >> 8);
-      p[3] = (uint8_t)(v >> 24);
-    }
-  } else {
-    if (r == 0u) {
-      *(uint64_t*)p = v;
-      return;
-    }
-    const uint32_t h = 8u - r;  // bytes up to the boundary
-    if (h & 1u) { *p = (uint8_t)v; p += 1; v >>= 8; }
-    if (h & 2u) { *(uint16_t*)p = (uint16_t)v; p += 2; v >>= 16; }
-    if (h & 4u) { *(uint32_t*)p = (uint32_t)v; p += 4; v >>= 32; }
-    if (r & 4u) { *(uint32_t*)p = (uint32_t)v; p += 4; v >>= 32; }
-    if (r & 2u) { *(uint16_t*)p = (uint16_t)v; p += 2; v >>= 16; }
-    if (r & 1u) *p = (uint8_t)v;
-  }
-}
-
-template <uint32_t AB>
-__device__ __forceinline__ bool fits(uint64_t v) {
-  return AB >= 8u || (v >> (8u * (AB & 7u))) == 0ull;
-}
+// (the byte fields — Bounds, rd_le, wr_le, fits — are blob.h's)
 
 // ------------------------------------------------------------------ framing
 // The length words of one blob against the bytes it has. n[c] entries of
@@ -151,38 +88,7 @@ __device__ __forceinline__ Frame frame(const uint8_t* blobs, uint64_t blob_bytes
 }
 
 // ---------------------------------------------------------------- flat walk
-__device__ __forceinline__ uint64_t wave_incl_scan(uint64_t v, uint32_t lane) {
-#pragma unroll
-  for (uint32_t d = 1; d < kW; d <<= 1) {
-    const uint64_t u = rd64(v, (lane - d) & 63u);
-    if (lane >= d) v += u;
-  }
-  return v;
-}
-
-// Lane k stands for an object of n entries. Calls f(t, k, has) for every entry
-// of the 64 objects, 64 entries a step: `has` says the lane holds an entry,
-// which is entry k of lane t's object; the lane below holds entry k - 1 of the
-// same object except in lane 0. Every lane makes every call. The sum of the 64
-// counts must fit a u64.
-template <class F>
-__device__ __forceinline__ void flat_walk(uint64_t n, uint32_t lane, F f) {
-  const uint64_t e = wave_incl_scan(n, lane), b = e - n;
-  for_each_in_ranges(true, true, b, e, lane,
-                     [&](uint64_t j, bool has, uint32_t t) { f(t, j - rd64(b, t), has); });
-}
-
-// bit t: some lane says `bad` of lane t's object
-__device__ __forceinline__ uint64_t owners(bool bad, uint32_t t) {
-  uint64_t m = __ballot(bad), r = 0;
-  while (m) {
-    const uint32_t l = (uint32_t)__builtin_ctzll(m);
-    m &= m - 1u;
-    r |= 1ull << lane32(t, l);
-  }
-  return r;
-}
-
+// (flat_walk and owners are csr_rank.h's)
 // The entries of one clock of 64 blobs (lane k: n entries from byte pos of
 // blobs). Canonical form per entry: counter > 0, actor < limit, actor above
 // the entry before it (lane below, or re-read in lane 0: a clock's first

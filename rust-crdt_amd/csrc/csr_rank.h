@@ -1,7 +1,8 @@
 // Wave-level helpers of the CSR clock kernels (csr_merge.hip, clock_ops.hip,
-// read.hip, lwwreg.hip, clock_bincode.hip): the ds_bpermute cross-lane reads,
-// the rank of an actor in a sorted run held in registers (<= 64 entries, one
-// per lane) or in HBM, and the flat walk over the op ranges of 64 objects. The
+// read.hip, lwwreg.hip, clock_bincode.hip, ops_bincode.hip): the ds_bpermute
+// cross-lane reads, the rank of an actor in a sorted run held in registers
+// (<= 64 entries, one per lane) or in HBM, the flat walk over the op ranges of
+// 64 objects, and over 64 counts with the owner mask of its bad entries. The
 // readlane reads (lane32 / lane64), the ballot prefix count (mbcnt) and fail
 // are wave.h's, seen through namespace csr_rank.
 #pragma once
@@ -72,6 +73,38 @@ __device__ __forceinline__ void for_each_in_ranges(bool valid, bool good, uint64
       for (uint64_t j0 = bb; j0 < ee; j0 += 64u) f(j0 + lane, j0 + lane < ee, t);
     }
   }
+}
+
+__device__ __forceinline__ uint64_t wave_incl_scan(uint64_t v, uint32_t lane) {
+#pragma unroll
+  for (uint32_t d = 1; d < kW; d <<= 1) {
+    const uint64_t u = rd64(v, (lane - d) & 63u);
+    if (lane >= d) v += u;
+  }
+  return v;
+}
+
+// Lane k stands for an object of n entries. Calls f(t, k, has) for every entry
+// of the 64 objects, 64 entries a step: `has` says the lane holds an entry,
+// which is entry k of lane t's object; the lane below holds entry k - 1 of the
+// same object except in lane 0. Every lane makes every call. The sum of the 64
+// counts must fit a u64.
+template <class F>
+__device__ __forceinline__ void flat_walk(uint64_t n, uint32_t lane, F f) {
+  const uint64_t e = wave_incl_scan(n, lane), b = e - n;
+  for_each_in_ranges(true, true, b, e, lane,
+                     [&](uint64_t j, bool has, uint32_t t) { f(t, j - rd64(b, t), has); });
+}
+
+// bit t: some lane says `bad` of lane t's object
+__device__ __forceinline__ uint64_t owners(bool bad, uint32_t t) {
+  uint64_t m = __ballot(bad), r = 0;
+  while (m) {
+    const uint32_t l = (uint32_t)__builtin_ctzll(m);
+    m &= m - 1u;
+    r |= 1ull << lane32(t, l);
+  }
+  return r;
 }
 
 // # of entries of the sorted run a[0, n) (in HBM) below x.

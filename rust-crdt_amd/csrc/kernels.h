@@ -151,6 +151,19 @@ int launch_clock_ops_to_bincode(const uint32_t* actor, const uint64_t* counter, 
                                 uint32_t ab, bool with_dir, uint8_t* blobs, uint64_t stride, int* status,
                                 hipStream_t stream);
 
+// bincode codec of the Orswot, MVReg and Map op streams (ops_bincode.hip; the
+// ABI functions in api.hip validate). W: every width in {1, 2, 4, 8} (the
+// caller sets the ones op_type does not use to 8); A: the arrays op_type uses
+// are non-null. Egest: out == nullptr is the sizes pass.
+int launch_ops_bincode_clk_lens(const uint8_t* blobs, uint64_t blob_bytes, const uint64_t* boff, const uint64_t* blen,
+                                uint64_t n_ops, uint32_t op_type, const crdt_op_widths& W, uint32_t* clk_len,
+                                int* status, hipStream_t stream);
+int launch_ops_from_bincode(const uint8_t* blobs, uint64_t blob_bytes, const uint64_t* boff, const uint64_t* blen,
+                            uint32_t op_type, const crdt_op_widths& W, const crdt_op_arrays& A, uint32_t* op_err,
+                            int* status, hipStream_t stream);
+int launch_ops_to_bincode(uint32_t op_type, const crdt_op_widths& W, const crdt_op_arrays& A, uint64_t* sizes,
+                          uint8_t* out, const uint64_t* ooff, uint64_t out_bytes, int* status, hipStream_t stream);
+
 // The read path (read.hip): exactly one of sizes / out is non-null (the sizes
 // call / the write call); the same kernel, so the two cannot disagree.
 int launch_orswot_read(const crdt_orswot_batch& B, const crdt_read_queries& Q, uint32_t A, uint32_t flags,
