@@ -1079,6 +1079,58 @@ int crdt_mvreg_merge(crdt_ctx* ctx, const uint32_t* d_self_n, const uint64_t* d_
                      size_t n_obj, uint32_t n_actors, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * crdt_mvreg_fold: out[i] = reps[0][i].merge(reps[1][i]).merge(reps[2][i])...
+ * (src/mvreg.rs:121-153) in rank order, the fixed-order convention of
+ * crdt_orswot_fold and crdt_lwwreg_fold, over crdt_mvreg_merge's slabs. One
+ * launch: every replica's used slots are read once, the output is written
+ * once, no intermediate register goes through HBM and the host is not
+ * synchronised. h_reps is a HOST array of n_reps views. The output follows
+ * the merge's convention (survivors in the reference's order, every unused
+ * slot of d_out_clk / d_out_val zero-filled); n_reps == 1 copies replica 0
+ * through, n_reps == 2 gives crdt_mvreg_merge's bytes. No slot past n[i] of
+ * any replica takes part (the pipeline may load it, inside the slab, as the
+ * merge's does).
+ *
+ * The rule, with (r, k) for used slot k of replica r and `>` for strictly
+ * greater under VClock::partial_cmp: (r, k) is dropped when a used slot of
+ * another replica is > it (a slot only its own replica dominates is kept, as
+ * merge keeps it); otherwise it is kept when r == 0 (duplicates inside
+ * replica 0 too); otherwise it is dropped when an equal clock sits at an
+ * earlier slot of replica r, or in an earlier replica while no slot of
+ * replica r is > this clock; survivors come out in (r, k) order.
+ *
+ * CRDT_EINVAL, before any device work: null ctx or h_reps; n_reps 0 or >
+ * CRDT_MVREG_MAX_REPS; any cap 0 or > 1024; T = the caps' sum > 2048; out_cap
+ * 0 or > 2048; n_actors 0; a null array with n_obj > 0; an output array equal
+ * to a replica's array (not in place). n_obj == 0 is CRDT_OK, launches and
+ * writes nothing, null arrays included (the capacities are still checked).
+ * Latched per object as in the merge (its output left unwritten, every other
+ * object folded): CRDT_ENONCANON for any n[r][i] > cap_r, CRDT_ECAPACITY for
+ * more survivors than out_cap — the final count; the chain's intermediate
+ * registers do not exist here.
+ *
+ * Tiers: T <= 64 and a wave's LDS of 8 T n_actors + 18 T bytes, rounded
+ * up to 16, within 60 KB take the fast kernel (one wave per register, as
+ * many waves per block, 4 at the most, as 60 KB allow); everything else a
+ * one-wave-per-register kernel comparing the rows in HBM.
+ *
+ * Fold or chain (measured, 4M registers, 16 actors, 4 slots per replica,
+ * DESIGN.md §5v): the fold is the faster at every R measured — 0.74x one
+ * crdt_mvreg_merge at R = 2, 0.44x the chain of R - 1 merges at R = 4 and
+ * 0.29x at R = 8 — and needs no intermediate slabs.
+ * ------------------------------------------------------------------------ */
+#define CRDT_MVREG_MAX_REPS 32
+typedef struct crdt_mvreg_view {   /* one replica's registers, device arrays, crdt_mvreg_merge's slab */
+  const uint32_t* n;    /* [n_obj] slots in use */
+  const uint64_t* clk;  /* [n_obj][cap][n_actors], 0 = absent */
+  const uint64_t* val;  /* [n_obj][cap] */
+  uint32_t cap;
+} crdt_mvreg_view;
+int crdt_mvreg_fold(crdt_ctx* ctx, const crdt_mvreg_view* h_reps, uint32_t n_reps,
+                    uint32_t* d_out_n, uint64_t* d_out_clk, uint64_t* d_out_val, uint32_t out_cap,
+                    size_t n_obj, uint32_t n_actors, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * MVReg<u64, A> op path, batched, over crdt_mvreg_merge's slabs (n[i] slots
  * in use, clk[i][cap][n_actors] dense rows with 0 = absent, val[i][cap], Vec
  * order). Outputs follow the merge's convention: survivors in order, every

@@ -1319,6 +1319,26 @@ class Engine(LWWEngine, ClockBincodeEngine, OpsBincodeEngine):
             self.status(stream)
         return outn, outc, outv
 
+    def mvreg_fold(self, reps, n_actors, out_cap=None, out=None, stream=None, check_status=True):
+        """reps[0].merge(reps[1]).merge(reps[2])... in rank order, one launch
+        (crdt_mvreg_fold): `reps` is a list of 1..32 slabs (n, clocks[n][cap][A],
+        vals[n][cap]) as mvreg_merge takes them, capacities of their own (each
+        <= 1024, 2048 in all); returns the output slab (`out`, or a new one of
+        out_cap slots, default: the capacities' sum, 2048 at the most). Not in place."""
+        from ._lib import MVRegViewC
+
+        p = lambda t: t.data_ptr() or None  # noqa: E731
+        views = (MVRegViewC * max(1, len(reps)))(*[MVRegViewC(p(n), p(c), p(v), int(v.shape[1])) for n, c, v in reps])
+        n_obj = int(reps[0][0].numel()) if reps else 0
+        total = sum(int(v.shape[1]) for _, _, v in reps)
+        cap = int(out[2].shape[1]) if out is not None else (out_cap or min(total, 2048))
+        outn, outc, outv = self._mvreg_out(n_obj, cap, n_actors, reps[0][0].device if reps else None, out)
+        check(lib.crdt_mvreg_fold(self.ctx, views, len(reps), C.c_void_p(p(outn)), C.c_void_p(p(outc)),
+                                  C.c_void_p(p(outv)), cap, n_obj, n_actors, self._stream(stream)), "mvreg_fold")
+        if check_status:
+            self.status(stream)
+        return outn, outc, outv
+
     def _mvreg_out(self, n_obj, cap, n_actors, dev, out):
         torch = _torch()
         if out is not None:

@@ -92,7 +92,7 @@ EXPORTS = [
     "crdt_vclock_csr_apply", "crdt_gcounter_csr_apply", "crdt_gcounter_csr_value", "crdt_vclock_csr_get",
     "crdt_orswot_read_sizes", "crdt_orswot_read", "crdt_map_read_sizes", "crdt_map_read", "crdt_map_mvreg_get",
     "crdt_lwwreg_merge", "crdt_lwwreg_apply", "crdt_lwwreg_fold", "crdt_lwwreg_from_bincode",
-    "crdt_lwwreg_to_bincode",
+    "crdt_lwwreg_to_bincode", "crdt_mvreg_fold",
     "crdt_clock_dense_from_bincode", "crdt_clock_dense_bincode_sizes", "crdt_clock_dense_to_bincode",
     "crdt_clock_csr_bincode_lens", "crdt_clock_csr_from_bincode", "crdt_clock_csr_bincode_sizes",
     "crdt_clock_csr_to_bincode", "crdt_clock_ops_from_bincode", "crdt_clock_ops_to_bincode",
@@ -196,6 +196,11 @@ class LWWOpsC(C.Structure):
 class LWWViewC(C.Structure):
     """crdt_lwwreg_view (include/crdts_hip.h)."""
     _fields_ = [("val", C.c_void_p), ("marker", C.c_void_p)]
+
+
+class MVRegViewC(C.Structure):
+    """crdt_mvreg_view (include/crdts_hip.h)."""
+    _fields_ = [("n", C.c_void_p), ("clk", C.c_void_p), ("val", C.c_void_p), ("cap", C.c_uint32)]
 
 
 class ReadQueriesC(C.Structure):
@@ -391,6 +396,7 @@ def _load():
         "crdt_lwwreg_merge": (I, [P, P, P, P, P, SZ, U32, P, P, P]),
         "crdt_lwwreg_apply": (I, [P, P, P, C.POINTER(LWWOpsC), SZ, U32, P, P, P]),
         "crdt_lwwreg_fold": (I, [P, C.POINTER(LWWViewC), U32, SZ, U32, P, P, P, P]),
+        "crdt_mvreg_fold": (I, [P, C.POINTER(MVRegViewC), U32, P, P, P, U32, SZ, U32, P]),
         "crdt_lwwreg_from_bincode": (I, [P, P, SZ, SZ, U32, U32, U32, U32, P, P, P]),
         "crdt_lwwreg_to_bincode": (I, [P, P, P, SZ, U32, U32, U32, U32, P, SZ, P]),
         "crdt_clock_dense_from_bincode": (I, [P, P, SZ, P, P, SZ, U32, U32, U32, P, P]),

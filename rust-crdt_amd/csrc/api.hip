@@ -731,6 +731,33 @@ int crdt_mvreg_merge(crdt_ctx* ctx, const uint32_t* d_self_n, const uint64_t* d_
                             S(stream));
 }
 
+int crdt_mvreg_fold(crdt_ctx* ctx, const crdt_mvreg_view* h_reps, uint32_t n_reps, uint32_t* d_out_n,
+                    uint64_t* d_out_clk, uint64_t* d_out_val, uint32_t out_cap, size_t n_obj, uint32_t n_actors,
+                    void* stream) {
+  if (!ctx || !h_reps || n_reps == 0 || n_reps > CRDT_MVREG_MAX_REPS || n_actors == 0 || out_cap == 0 ||
+      out_cap > 2048)
+    return CRDT_EINVAL;
+  uint32_t total = 0;
+  for (uint32_t r = 0; r < n_reps; ++r) {
+    if (h_reps[r].cap == 0 || h_reps[r].cap > 1024) return CRDT_EINVAL;
+    total += h_reps[r].cap;
+  }
+  if (total > 2048) return CRDT_EINVAL;
+  if (n_obj) {
+    if (!d_out_n || !d_out_clk || !d_out_val) return CRDT_EINVAL;
+    for (uint32_t r = 0; r < n_reps; ++r) {
+      if (!h_reps[r].n || !h_reps[r].clk || !h_reps[r].val) return CRDT_EINVAL;
+      for (const void* w : {(const void*)d_out_n, (const void*)d_out_clk, (const void*)d_out_val})  // not in place
+        if (w == h_reps[r].n || w == h_reps[r].clk || w == h_reps[r].val) return CRDT_EINVAL;
+    }
+  }
+  if (n_obj == 0) return CRDT_OK;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_mvreg_fold(h_reps, n_reps, d_out_n, d_out_clk, d_out_val, out_cap, n_obj, n_actors, ctx->d_status,
+                           S(stream));
+}
+
 static bool mvreg_op_caps_ok(uint32_t self_cap, uint32_t out_cap, uint32_t n_actors) {
   return n_actors && self_cap && self_cap <= 1024 && out_cap >= self_cap && out_cap <= 2048;
 }

@@ -99,6 +99,11 @@ int launch_mvreg_merge(const uint32_t* sn, const uint64_t* sclk, const uint64_t*
                        uint64_t* outclk, uint64_t* outval, uint32_t outcap, uint64_t n_obj, uint32_t A, int* status,
                        hipStream_t stream);
 
+// MVReg fold (mvreg_fold.hip): reps is a host array; 1 <= n_reps <= 32, every
+// cap in [1, 1024], their sum <= 2048 (api.hip checks the rest)
+int launch_mvreg_fold(const crdt_mvreg_view* reps, uint32_t n_reps, uint32_t* outn, uint64_t* outclk, uint64_t* outval,
+                      uint32_t outcap, uint64_t n_obj, uint32_t A, int* status, hipStream_t stream);
+
 // MVReg op path (mvreg_apply.hip): Put lists, truncate, the read clock;
 // self_cap <= out_cap within the ABI limits (api.hip)
 int launch_mvreg_apply(const uint32_t* sn, const uint64_t* sclk, const uint64_t* sval, uint32_t scap,
