@@ -1282,16 +1282,43 @@ int crdt_orswot_apply(crdt_ctx* ctx, const crdt_orswot_batch* self, const crdt_o
  * [out_cap]; Vec order, unused slots zero-filled), ready for crdt_mvreg_merge,
  * crdt_mvreg_apply and crdt_mvreg_read_clock. An absent key and an ALL query
  * give n = 0. Only kind and key of the queries are read.
- * Out of scope: the value of get for Map<u64, Orswot> and the nested map (a
- * slab-to-record conversion); their ctx (val, slot, clocks) is served by the
- * common view.
+ * crdt_map_orswot_get*: the val of Map::get for Map<u64, Orswot> as a batch
+ * of canonical records, two calls like the ingest codec. *_get_sizes writes
+ * d_sizes[j], the bytes of query j's record (a multiple of 16), and, if
+ * d_present is not null, 1 where the record is the key's value; the caller
+ * places the records at 16-B aligned offsets (an exclusive scan of the sizes);
+ * the write call puts record j at d_out + d_out_off[j]. (d_out, d_out_off, n_q,
+ * out_bytes) is then a crdt_orswot_batch of n_q records with dense top clocks
+ * (n_clk == n_actors, flags 0), valid input wherever a merge output is. The
+ * record is the canonical form of the slab value: clk = the vclock row,
+ * mem_key = vmem[0, vn_mem), member m's dots = the non-zero slots of vmclock[m]
+ * (actors ascending), mem_dend their cumulative ends, the deferred clocks = the
+ * non-zero slots of vdclock[d] in the slab's own CLOCK ORDER, their sets =
+ * vdset[d][0, vdset_n[d]); padding bytes are zero. A member whose vmclock row
+ * is all zero is kept as an empty run and the header gets
+ * CRDT_ORSWOT_EMPTY_MEMBER_CLOCK. An absent key and an ALL query give present
+ * 0 and the record of Orswot::default() (a header and a zero clock): what
+ * Map::update hands its closure for a missing key; the batch stays dense in
+ * n_q. The write call counts again: it never trusts the sizes call.
+ * crdt_map_map_get: the val of get for the nested map: query j's inner map
+ * (object i * kcap + slot of `inner`) is copied into row j of `out`, a
+ * crdt_map_mvreg_slab of n_q rows that crdt_map_mvreg_merge / _apply /
+ * _truncate / _to_bincode and crdt_map_read accept. The counts and the clock
+ * row are always written, otherwise only the used slots (the Map slabs'
+ * convention). An absent key and an ALL query give present 0, n_keys = n_def
+ * = 0 and a zero clock: Map::default(). out's capacities may exceed inner's.
+ * Both read only obj_end, kind and key of the queries, and a located value by
+ * its used counts, never by its capacities.
  *
  * CRDT_EINVAL (before any device work): a null ctx or struct; with n_obj > 0 a
  * null batch / view array or obj_end; with n_q > 0 a null kind or key, (write
  * call) a wanted group's null array, (crdt_map_mvreg_get) a null output or
  * nested array; n_actors == 0 (maps: or > 128); kcap == 0 or > 8192; flags
  * other than 0 or CRDT_ORSWOT_SPARSE_CLOCK; an output array equal to an input
- * array; out_cap < slab.mcap. Otherwise n_obj == 0 is CRDT_OK.
+ * array; out_cap < slab.mcap; (crdt_map_orswot_get*, crdt_map_map_get) with
+ * n_obj > 0 a null array of those the call reads, with n_q > 0 a null d_sizes,
+ * d_out or array of `out`, a null d_out_off, an `out` capacity below inner's.
+ * Otherwise n_obj == 0 is CRDT_OK.
  * Latched (crdt_ctx_status), the other queries and objects unaffected:
  *   CRDT_ENONCANON  an obj_end that decreases or runs past n_q (the object's
  *                   queries are not written, as in crdt_vclock_dense_get); a
@@ -1304,9 +1331,19 @@ int crdt_orswot_apply(crdt_ctx* ctx, const crdt_orswot_batch* self, const crdt_o
  *                   the reference's inc overflows (src/vclock.rs:182-185):
  *                   dot_ctr 0, the query answered as without an actor;
  *                   crdt_map_mvreg_get: a register count above mcap (n = 0).
+ *                   crdt_map_orswot_get*, crdt_map_map_get: a located value
+ *                   whose counts exceed its capacities (vn_mem > mcap, vn_def
+ *                   > vdcap, vdset_n > vscap; n_keys, mv_n, n_def or dset_n
+ *                   above inner's) or that a record cannot hold (an all-zero
+ *                   deferred clock row, an empty deferred set): the query gets
+ *                   the default record or row and present 0, in both calls;
+ *                   an unknown kind gives the object's queries the same.
  *   CRDT_ECAPACITY  (write call) a span end[j] - end[j-1] that is not the
  *                   query's length or leaves [0, n): the query's group is not
  *                   written; nothing outside the arrays is touched.
+ *                   crdt_map_orswot_get: a d_out_off[j] that is not 16-B
+ *                   aligned or whose record leaves [0, out_bytes): that record
+ *                   is not written; nothing outside d_out is touched.
  * Sortedness is taken as given (as crdt_vclock_csr_get): no deep validation.
  * ------------------------------------------------------------------------ */
 #define CRDT_READ_KEY 0u            /* Orswot::contains(member) / Map::get(key)            */
@@ -1347,6 +1384,13 @@ int crdt_map_read(crdt_ctx* ctx, const crdt_map_read_view* view, const crdt_read
 int crdt_map_mvreg_get(crdt_ctx* ctx, const crdt_map_mvreg_slab* slab, const crdt_read_queries* queries,
                        size_t n_obj, uint32_t n_actors, uint32_t* d_out_n, uint64_t* d_out_clk,
                        uint64_t* d_out_val, uint32_t out_cap, void* stream);
+int crdt_map_orswot_get_sizes(crdt_ctx* ctx, const crdt_map_orswot_slab* slab, const crdt_read_queries* queries,
+                              size_t n_obj, uint32_t n_actors, uint64_t* d_sizes, uint32_t* d_present, void* stream);
+int crdt_map_orswot_get(crdt_ctx* ctx, const crdt_map_orswot_slab* slab, const crdt_read_queries* queries,
+                        size_t n_obj, uint32_t n_actors, uint8_t* d_out, const uint64_t* d_out_off, size_t out_bytes,
+                        void* stream);
+int crdt_map_map_get(crdt_ctx* ctx, const crdt_map_map_slab* slab, const crdt_read_queries* queries, size_t n_obj,
+                     uint32_t n_actors, const crdt_map_mvreg_slab* out, uint32_t* d_present, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * Ingest / egest: the reference's binary form <-> canonical records

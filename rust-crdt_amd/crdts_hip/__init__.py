@@ -1711,6 +1711,54 @@ class Engine(LWWEngine, ClockBincodeEngine, OpsBincodeEngine):
             self.status(stream)
         return outn, outc, outv
 
+    def map_orswot_get(self, S: "MapOrswotSlab", queries: "ReadQueries", n_actors, stream=None, check_status=True):
+        """The value of Map::get (src/map.rs:291-302) for Map<u64, Orswot>: query
+        j's set as record j of an OrswotBatch (dense top clocks), packed back to
+        back: the sizes call, an exclusive scan, the write call. Returns (batch,
+        present): present[j] = 1 where the record is the key's value; an absent
+        key and an ALL query give Orswot::default()."""
+        torch = _torch()
+        dev = S.a["n_keys"].device
+        n_q, n = queries.n_q, S.n
+        st = self._stream(stream)
+        s, q = S.cstruct(), queries.cqueries()
+        sizes = torch.zeros(n_q, dtype=torch.int64, device=dev)
+        present = torch.zeros(n_q, dtype=torch.int32, device=dev)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None  # noqa: E731
+        check(lib.crdt_map_orswot_get_sizes(self.ctx, C.byref(s), C.byref(q), n, n_actors, p(sizes), p(present), st),
+              "map_orswot_get_sizes")
+        with torch.cuda.stream(stream) if stream is not None else _nullctx():
+            ends = torch.cumsum(sizes, 0)
+            total = int(ends[-1].item()) if n_q else 0
+            off = ends - sizes
+        base = torch.empty(max(16, total), dtype=torch.uint8, device=dev)
+        check(lib.crdt_map_orswot_get(self.ctx, C.byref(s), C.byref(q), n, n_actors, C.c_void_p(base.data_ptr()),
+                                      p(off), int(base.numel()), st), "map_orswot_get")
+        if check_status:
+            self.status(stream)
+        return OrswotBatch(base, off, n_actors, int(base.numel()), 0), present
+
+    def map_map_get(self, S: "MapMapSlab", queries: "ReadQueries", n_actors, out=None, stream=None,
+                    check_status=True):
+        """The value of Map::get for the nested map: query j's inner map as row j
+        of a MapSlab (allocated at S.inner's capacities when out is None), ready
+        for map_mvreg_merge / _apply / _truncate / _to_bincode and map_read.
+        Returns (slab, present); an absent key and an ALL query give the empty
+        map."""
+        torch = _torch()
+        dev = S.a["n_keys"].device
+        n_q = queries.n_q
+        if out is None:
+            out = MapSlab.alloc(n_q, n_actors, *S.inner_caps, device=dev)
+        present = torch.zeros(n_q, dtype=torch.int32, device=dev)
+        s, q, o = S.cstruct(), queries.cqueries(), out.cstruct()
+        check(lib.crdt_map_map_get(self.ctx, C.byref(s), C.byref(q), S.n, n_actors, C.byref(o),
+                                   C.c_void_p(present.data_ptr()) if n_q else None, self._stream(stream)),
+              "map_map_get")
+        if check_status:
+            self.status(stream)
+        return out, present
+
     # ------------------------------------------------ bincode ingest / egest
     def orswot_from_bincode(self, blobs, blob_off, blob_len, n_actors, actor_bytes, member_bytes, flags=0,
                             stream=None, check_status=True, packed=True):

@@ -91,6 +91,7 @@ EXPORTS = [
     "crdt_vclock_dense_get", "crdt_vclock_csr_truncate", "crdt_vclock_csr_subtract", "crdt_vclock_csr_intersection",
     "crdt_vclock_csr_apply", "crdt_gcounter_csr_apply", "crdt_gcounter_csr_value", "crdt_vclock_csr_get",
     "crdt_orswot_read_sizes", "crdt_orswot_read", "crdt_map_read_sizes", "crdt_map_read", "crdt_map_mvreg_get",
+    "crdt_map_orswot_get_sizes", "crdt_map_orswot_get", "crdt_map_map_get",
     "crdt_lwwreg_merge", "crdt_lwwreg_apply", "crdt_lwwreg_fold", "crdt_lwwreg_from_bincode",
     "crdt_lwwreg_to_bincode", "crdt_mvreg_fold",
     "crdt_clock_dense_from_bincode", "crdt_clock_dense_bincode_sizes", "crdt_clock_dense_to_bincode",
@@ -393,6 +394,10 @@ def _load():
                                     C.POINTER(ReadSizesC), P]),
         "crdt_map_read": (I, [P, C.POINTER(MapReadViewC), C.POINTER(ReadQueriesC), SZ, U32, C.POINTER(ReadOutC), P]),
         "crdt_map_mvreg_get": (I, [P, C.POINTER(MapSlabC), C.POINTER(ReadQueriesC), SZ, U32, P, P, P, U32, P]),
+        "crdt_map_orswot_get_sizes": (I, [P, C.POINTER(MapOrswotSlabC), C.POINTER(ReadQueriesC), SZ, U32, P, P, P]),
+        "crdt_map_orswot_get": (I, [P, C.POINTER(MapOrswotSlabC), C.POINTER(ReadQueriesC), SZ, U32, P, P, SZ, P]),
+        "crdt_map_map_get": (I, [P, C.POINTER(MapMapSlabC), C.POINTER(ReadQueriesC), SZ, U32, C.POINTER(MapSlabC), P,
+                                 P]),
         "crdt_lwwreg_merge": (I, [P, P, P, P, P, SZ, U32, P, P, P]),
         "crdt_lwwreg_apply": (I, [P, P, P, C.POINTER(LWWOpsC), SZ, U32, P, P, P]),
         "crdt_lwwreg_fold": (I, [P, C.POINTER(LWWViewC), U32, SZ, U32, P, P, P, P]),

@@ -1287,6 +1287,67 @@ int crdt_map_mvreg_get(crdt_ctx* ctx, const crdt_map_mvreg_slab* slab, const crd
                               ctx->d_status, S(stream));
 }
 
+namespace {
+int map_orswot_get(crdt_ctx* ctx, const crdt_map_orswot_slab* slab, const crdt_read_queries* q, size_t n_obj,
+                   uint32_t n_actors, uint64_t* d_sizes, uint32_t* d_present, uint8_t* d_out,
+                   const uint64_t* d_out_off, size_t out_bytes, bool write, void* stream) {
+  if (!ctx || !slab || !map_actors_ok(n_actors) || !cap_ok(slab->kcap, kReadKcapMax) || !read_queries_ok(q, n_obj))
+    return CRDT_EINVAL;
+  // what the get reads: the key search's arrays and the nested Orswots
+  const std::initializer_list<const void*> state = {slab->n_keys, slab->keys,    slab->vclock,  slab->vn_mem,
+                                                    slab->vmem,   slab->vmclock, slab->vn_def,  slab->vdclock,
+                                                    slab->vdset_n, slab->vdset};
+  if (n_obj)
+    for (const void* r : state)
+      if (!r) return CRDT_EINVAL;
+  if (q->n_q && (write ? (!d_out_off || (n_obj && !d_out)) : !d_sizes)) return CRDT_EINVAL;
+  for (const void* w : {(const void*)d_sizes, (const void*)d_present, (const void*)d_out})
+    if (read_alias(w, q, state) || (w && w == (const void*)d_out_off)) return CRDT_EINVAL;
+  if (d_out_off && read_alias(d_out_off, q, {})) return CRDT_EINVAL;
+  if (d_sizes && (const void*)d_sizes == (const void*)d_present) return CRDT_EINVAL;
+  if (n_obj == 0) return CRDT_OK;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_map_orswot_get(*slab, *q, n_obj, n_actors, d_sizes, d_present, d_out, d_out_off, out_bytes,
+                               ctx->d_status, S(stream));
+}
+}  // namespace
+
+int crdt_map_orswot_get_sizes(crdt_ctx* ctx, const crdt_map_orswot_slab* slab, const crdt_read_queries* queries,
+                              size_t n_obj, uint32_t n_actors, uint64_t* d_sizes, uint32_t* d_present, void* stream) {
+  return map_orswot_get(ctx, slab, queries, n_obj, n_actors, d_sizes, d_present, nullptr, nullptr, 0, false, stream);
+}
+int crdt_map_orswot_get(crdt_ctx* ctx, const crdt_map_orswot_slab* slab, const crdt_read_queries* queries,
+                        size_t n_obj, uint32_t n_actors, uint8_t* d_out, const uint64_t* d_out_off, size_t out_bytes,
+                        void* stream) {
+  return map_orswot_get(ctx, slab, queries, n_obj, n_actors, nullptr, nullptr, d_out, d_out_off, out_bytes, true,
+                        stream);
+}
+int crdt_map_map_get(crdt_ctx* ctx, const crdt_map_map_slab* slab, const crdt_read_queries* queries, size_t n_obj,
+                     uint32_t n_actors, const crdt_map_mvreg_slab* out, uint32_t* d_present, void* stream) {
+  if (!ctx || !slab || !out || !map_actors_ok(n_actors) || !cap_ok(slab->kcap, kReadKcapMax) ||
+      !read_queries_ok(queries, n_obj))
+    return CRDT_EINVAL;
+  const crdt_map_mvreg_slab* in = &slab->inner;
+  if (in->kcap == 0 || out->kcap < in->kcap || out->mcap < in->mcap || out->dcap < in->dcap || out->scap < in->scap)
+    return CRDT_EINVAL;
+  if (n_obj && (!slab->n_keys || !slab->keys || !ptrs_ok(in))) return CRDT_EINVAL;
+  if (n_obj && queries->n_q && !ptrs_ok(out)) return CRDT_EINVAL;
+  const std::initializer_list<const void*> state = {slab->n_keys, slab->keys,     in->clock, in->n_keys,
+                                                    in->keys,     in->eclock,     in->mv_n,  in->mv_clock,
+                                                    in->mv_val,   in->n_def,      in->dclock, in->dset_n,
+                                                    in->dset};
+  for (const void* w : {(const void*)out->clock, (const void*)out->n_keys, (const void*)out->keys,
+                        (const void*)out->eclock, (const void*)out->mv_n, (const void*)out->mv_clock,
+                        (const void*)out->mv_val, (const void*)out->n_def, (const void*)out->dclock,
+                        (const void*)out->dset_n, (const void*)out->dset, (const void*)d_present})
+    if (read_alias(w, queries, state)) return CRDT_EINVAL;
+  if (n_obj == 0) return CRDT_OK;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_map_map_get(*slab, *queries, n_obj, n_actors, *out, d_present, ctx->d_status, S(stream));
+}
+
 // ------------------------------------------------------------------------
 // bincode of the Orswot, MVReg and Map ops (ops_bincode.hip)
 namespace {

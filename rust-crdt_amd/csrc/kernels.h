@@ -178,6 +178,14 @@ int launch_map_read(const crdt_map_read_view& V, const crdt_read_queries& Q, uin
 int launch_map_mvreg_get(const crdt_map_mvreg_slab& M, const crdt_read_queries& Q, uint64_t n_obj, uint32_t A,
                          uint32_t* out_n, uint64_t* out_clk, uint64_t* out_val, uint32_t out_cap, int* status,
                          hipStream_t stream);
+// Map<u64, Orswot>::get's value as records: sizes non-null = the sizes call
+// (present may be null), else the write call to out + ooff[j].
+int launch_map_orswot_get(const crdt_map_orswot_slab& M, const crdt_read_queries& Q, uint64_t n_obj, uint32_t A,
+                          uint64_t* sizes, uint32_t* present, uint8_t* out, const uint64_t* ooff, uint64_t out_bytes,
+                          int* status, hipStream_t stream);
+// The nested map's get value: query j's inner map as row j of out.
+int launch_map_map_get(const crdt_map_map_slab& M, const crdt_read_queries& Q, uint64_t n_obj, uint32_t A,
+                       const crdt_map_mvreg_slab& out, uint32_t* present, int* status, hipStream_t stream);
 
 int launch_map_mvreg_merge(const crdt_map_mvreg_slab& S, const crdt_map_mvreg_slab& O, const crdt_map_mvreg_slab& R,
                            uint64_t n_obj, uint32_t A, int* status, uint32_t* ctl, hipStream_t stream, int variant = 0);

@@ -3,7 +3,9 @@
 // (src/map.rs:282-302) and the contexts derived from them, ReadCtx::
 // derive_add_ctx / derive_rm_ctx (src/ctx.rs:45-60), over Orswot record
 // batches and over the outer arrays the three Map slabs share; and the value of
-// Map::get for Map<u64, MVReg> as rows of an MVReg slab.
+// Map::get: for Map<u64, MVReg> as rows of an MVReg slab, for Map<u64, Orswot>
+// as Orswot records (a slab-to-record conversion, two calls), for the nested
+// map as rows of a Map<u64, MVReg> slab (a gather by the used counts).
 //
 // Layout of a read. A wave takes 64 objects (lane k <-> object c + k: the query
 // ranges and, for objects that have queries, the record header or the row's
@@ -586,6 +588,340 @@ __global__ __launch_bounds__(kBlock) void mvreg_get_kernel(MapSrc S, const uint3
   }
 }
 
+// ---------------------------------------------------------------- Map<u64, Orswot>::get's and the nested map's value
+// The first step the three kernels below share with mvreg_get_kernel: a wave
+// takes 64 objects' query ranges and each lane finds its key; f(j, has, row,
+// found, lane, bad) is then called by every lane for every 64 queries: `row`
+// is the nested value's row (object * kcap + slot) where `found`.
+template <class F>
+__device__ __forceinline__ void for_each_located(const MapSrc& S, const crdt_read_queries& Q, uint64_t n_obj,
+                                                 uint64_t chunks, int* status, F f) {
+  const uint32_t lane = threadIdx.x & (kW - 1u);
+  const uint64_t wave = (uint64_t)blockIdx.x * (kBlock / kW) + threadIdx.x / kW;
+  const uint64_t n_waves = (uint64_t)gridDim.x * (kBlock / kW);
+  const Want w{false, false, false, false};
+  for (uint64_t ch = wave; ch < chunks; ch += n_waves) {
+    const uint64_t c0 = ch * kW, i = c0 + lane;
+    const bool valid = i < n_obj;
+    uint64_t b = 0, e = 0;
+    if (valid) {
+      e = Q.obj_end[i];
+      b = i ? Q.obj_end[i - 1u] : 0ull;
+    }
+    const bool good = b <= e && e <= Q.n_q;
+    bool bad = valid && !good;
+    Obj mine{0, 0, 0, 0, 0};
+    if (valid && good && e > b) mine = open_obj(S, i, bad);
+    close_unknown_kinds(Q, valid, good, b, e, lane, mine.ok, bad);
+    for_each_in_ranges(valid, good, b, e, lane, [&](uint64_t j, bool has, uint32_t t) {
+      const Obj o{rd64(mine.at, t), rd32(mine.n_clk, t), rd32(mine.n_mem, t), rd32(mine.n_dot, t), rd32(mine.ok, t)};
+      uint64_t row = 0;
+      bool found = false;
+      if (has) {
+        const Loc L = locate(S, o, Q.kind[j], Q.key[j], CRDT_READ_NO_ACTOR, w, bad);
+        found = L.slot != CRDT_READ_NO_SLOT;
+        row = found ? o.at * S.kcap + L.slot : 0ull;
+      }
+      f(j, has, row, found, lane, bad);
+    });
+    if (__ballot(bad) && lane == 0u) fail(status, CRDT_ENONCANON);
+  }
+}
+
+// The non-zero cells of `rows` dense clock rows of A cells each, contiguous at
+// p, walked row-major 64 cells a step (a row's end falls anywhere in a step):
+// cell(r, a, c, at) for slot a of row r holding c != 0, the at-th non-zero
+// cell (the wave prefix: mbcnt of the step's ballot plus the running base);
+// row_end(r, end) by the lane of row r's last slot, `end` the cells up to and
+// including the row's. A lane that ends a row without cells sets `hollow`.
+// Returns the number of cells. Arguments uniform; rows * A fits 32 bits.
+template <class F, class G>
+__device__ __forceinline__ uint32_t walk_rows(const uint64_t* p, uint32_t rows, uint32_t A, uint32_t lane, bool& hollow,
+                                              F cell, G row_end) {
+  const uint32_t cells = rows * A, dr = kW / A, da = kW % A;
+  uint32_t base = 0, last_end = 0, r = lane / A, a = lane % A;
+  for (uint32_t c0 = 0; c0 < cells; c0 += kW) {
+    const bool in = lane < cells - c0;
+    const uint64_t c = in ? p[c0 + lane] : 0ull;
+    const uint64_t m = __ballot(c != 0ull);
+    const uint32_t incl = base + mbcnt(m) + (c != 0ull ? 1u : 0u);
+    if (c) cell(r, a, c, incl - 1u);
+    const bool end = in && a == A - 1u;
+    // the end of the row before: A lanes below, or the last one of an earlier step
+    const uint32_t below = rd32(incl, (lane - A) & 63u);
+    const uint32_t prev = lane >= A ? below : last_end;
+    if (end) row_end(r, incl);
+    hollow |= end && incl == prev;
+    const uint64_t em = __ballot(end);
+    if (em) last_end = lane32(incl, 63u - (uint32_t)__builtin_clzll(em));
+    base += (uint32_t)__popcll(m);
+    r += dr;
+    a += da;
+    if (a >= A) {
+      a -= A;
+      ++r;
+    }
+  }
+  return base;
+}
+
+// The nested Orswots of a Map<u64, Orswot> slab.
+struct OrswotVals {
+  const uint64_t* vclock;
+  const uint32_t* vn_mem;
+  const uint64_t* vmem;
+  const uint64_t* vmclock;
+  const uint32_t* vn_def;
+  const uint64_t* vdclock;
+  const uint32_t* vdset_n;
+  const uint64_t* vdset;
+  uint32_t mcap, vdcap, vscap, A;
+};
+// The counts of a value's record and its size (record_size64: the formula of
+// crdt_orswot_record_bytes).
+struct ValCounts {
+  uint32_t n_mem, n_dot, n_def, n_def_dot, n_def_mem;
+  uint64_t size;
+};
+__device__ __forceinline__ ValCounts default_counts(uint32_t A) {
+  return ValCounts{0u, 0u, 0u, 0u, 0u, record_size64(A, 0u, 0u, 0u, 0u, 0u)};
+}
+
+// Counts the value at `row` by its used slots, for both calls. False: the
+// counts exceed the capacities, a deferred clock row is all zero, a deferred
+// set is empty, or the record would outgrow its 32-bit size — c is then the
+// default's. Arguments uniform.
+__device__ __forceinline__ bool count_value(const OrswotVals& V, uint64_t row, uint32_t lane, ValCounts& c) {
+  const uint32_t A = V.A;
+  c = default_counts(A);
+  const uint32_t nm = V.vn_mem[row], nd = V.vn_def[row];
+  if (nm > V.mcap || nd > V.vdcap || (uint64_t)nm * A > 0xffffffffull || (uint64_t)nd * A > 0xffffffffull)
+    return false;
+  uint64_t in_sets = 0;
+  bool bad_set = false;
+  for (uint32_t d0 = 0; d0 < nd; d0 += kW) {
+    const uint32_t d = d0 + lane;
+    const uint32_t n = d < nd ? V.vdset_n[row * V.vdcap + d] : 1u;
+    bad_set |= n == 0u || n > V.vscap;
+    in_sets += d < nd ? n : 0u;
+  }
+  if (__ballot(bad_set)) return false;
+  in_sets = lane64(wave_incl_scan(in_sets, lane), kW - 1u);
+  bool hollow = false;
+  const auto no_cell = [](uint32_t, uint32_t, uint64_t, uint32_t) {};
+  const auto no_end = [](uint32_t, uint32_t) {};
+  const uint32_t def_dot = walk_rows(V.vdclock + row * V.vdcap * A, nd, A, lane, hollow, no_cell, no_end);
+  if (__ballot(hollow)) return false;
+  const uint32_t dot = walk_rows(V.vmclock + row * V.mcap * A, nm, A, lane, hollow, no_cell, no_end);
+  if (in_sets > 0xffffffffull) return false;
+  const uint64_t size = record_size64(A, nm, dot, nd, def_dot, (uint32_t)in_sets);
+  if (size > 0xffffffffull) return false;
+  c = ValCounts{nm, dot, nd, def_dot, (uint32_t)in_sets, size};
+  return true;
+}
+
+// Writes the record of the value at `row` (`ok`: else the default record) with
+// counts c to R (16-B aligned, c.size bytes). Arguments uniform.
+__device__ __forceinline__ void write_value(const OrswotVals& V, uint64_t row, bool ok, const ValCounts& c, uint8_t* R,
+                                            uint32_t lane) {
+  const uint32_t A = V.A;
+  RecLayout L;
+  rec_layout(L, A, c.n_mem, c.n_dot, c.n_def, c.n_def_dot, c.n_def_mem);
+  uint64_t* clk = (uint64_t*)(R + L.o_clk);
+  for (uint32_t k = lane; k < A; k += kW) clk[k] = ok ? V.vclock[row * A + k] : 0ull;
+  uint32_t flags = 0u;
+  if (ok) {
+    uint64_t* key = (uint64_t*)(R + L.o_key);
+    for (uint32_t k = lane; k < c.n_mem; k += kW) key[k] = V.vmem[row * V.mcap + k];
+    uint64_t* dctr = (uint64_t*)(R + L.o_dctr);
+    uint32_t* dact = (uint32_t*)(R + L.o_dact);
+    uint32_t* mdend = (uint32_t*)(R + L.o_mdend);
+    bool hollow = false;
+    walk_rows(
+        V.vmclock + row * V.mcap * A, c.n_mem, A, lane, hollow,
+        [&](uint32_t, uint32_t a, uint64_t v, uint32_t at) {
+          if (at < c.n_dot) {
+            dctr[at] = v;
+            dact[at] = a;
+          }
+        },
+        [&](uint32_t r, uint32_t end) { mdend[r] = end; });
+    if (__ballot(hollow)) flags = CRDT_ORSWOT_EMPTY_MEMBER_CLOCK;
+    if (L.o_def != L.o_mpad && lane == 0u) *(uint32_t*)(R + L.o_mpad) = 0u;
+    uint64_t* fctr = (uint64_t*)(R + L.o_fctr);
+    uint64_t* fkey = (uint64_t*)(R + L.o_fkey);
+    uint32_t* fact = (uint32_t*)(R + L.o_fact);
+    uint32_t* fdend = (uint32_t*)(R + L.o_fdend);
+    uint32_t* fmend = (uint32_t*)(R + L.o_fmend);
+    walk_rows(
+        V.vdclock + row * V.vdcap * A, c.n_def, A, lane, hollow,
+        [&](uint32_t, uint32_t a, uint64_t v, uint32_t at) {
+          if (at < c.n_def_dot) {
+            fctr[at] = v;
+            fact[at] = a;
+          }
+        },
+        [&](uint32_t r, uint32_t end) { fdend[r] = end; });
+    uint32_t mbase = 0;
+    for (uint32_t d0 = 0; d0 < c.n_def; d0 += kW) {
+      const uint32_t d = d0 + lane;
+      const uint32_t n = d < c.n_def ? V.vdset_n[row * V.vdcap + d] : 0u;
+      const uint32_t incl = scan_incl(n, lane);
+      if (d < c.n_def) fmend[d] = mbase + incl;
+      const uint32_t cnt = c.n_def - d0 < kW ? c.n_def - d0 : kW;
+      for (uint32_t t = 0; t < cnt; ++t) {
+        const uint32_t nt = lane32(n, t), at = mbase + lane32(incl, t) - nt;
+        const uint64_t* src = V.vdset + (row * V.vdcap + d0 + t) * V.vscap;
+        for (uint32_t k = lane; k < nt; k += kW)
+          if (at + k < c.n_def_mem) fkey[at + k] = src[k];
+      }
+      mbase += lane32(incl, kW - 1u);
+    }
+  }
+  if (L.o_end + 4u * lane < L.size) *(uint32_t*)(R + L.o_end + 4u * lane) = 0u;
+  if (lane == 0u) {
+    uint4* h = (uint4*)R;
+    h[0] = make_uint4((uint32_t)c.size, A, c.n_mem, c.n_dot);
+    h[1] = make_uint4(c.n_def, c.n_def_dot, c.n_def_mem, flags);
+  }
+}
+
+// Query j's record size and whether it is a located value's.
+__global__ __launch_bounds__(kBlock) void map_orswot_get_sizes_kernel(MapSrc S, OrswotVals V, crdt_read_queries Q,
+                                                                      uint64_t* sizes, uint32_t* present,
+                                                                      uint64_t n_obj, uint64_t chunks, int* status) {
+  for_each_located(S, Q, n_obj, chunks, status,
+                   [&](uint64_t j, bool has, uint64_t row, bool found, uint32_t lane, bool& bad) {
+                     uint64_t size = default_counts(V.A).size;
+                     uint32_t pres = 0u;
+                     uint64_t pend = __ballot(has && found);
+                     while (pend) {
+                       const uint32_t u = (uint32_t)__builtin_ctzll(pend);
+                       pend &= pend - 1u;
+                       ValCounts c;
+                       const bool ok = count_value(V, lane64(row, u), lane, c);
+                       if (lane == u) {
+                         size = c.size;
+                         pres = ok ? 1u : 0u;
+                         bad |= !ok;
+                       }
+                     }
+                     if (has) {
+                       sizes[j] = size;
+                       if (present) present[j] = pres;
+                     }
+                   });
+}
+
+// Query j's record at out + ooff[j]: the counts are taken again, never from
+// the sizes call; a record that is misplaced is not written.
+__global__ __launch_bounds__(kBlock) void map_orswot_get_kernel(MapSrc S, OrswotVals V, crdt_read_queries Q,
+                                                                uint8_t* out, const uint64_t* ooff, uint64_t out_bytes,
+                                                                uint64_t n_obj, uint64_t chunks, int* status) {
+  for_each_located(S, Q, n_obj, chunks, status,
+                   [&](uint64_t j, bool has, uint64_t row, bool found, uint32_t lane, bool& bad) {
+                     const uint64_t off = has ? ooff[j] : 0ull;
+                     bool over = false;
+                     uint64_t pend = __ballot(has);
+                     while (pend) {
+                       const uint32_t u = (uint32_t)__builtin_ctzll(pend);
+                       pend &= pend - 1u;
+                       const bool fnd = lane32(found ? 1u : 0u, u) != 0u;
+                       const uint64_t ru = lane64(row, u), at = lane64(off, u);
+                       ValCounts c = default_counts(V.A);
+                       const bool ok = fnd && count_value(V, ru, lane, c);
+                       if (lane == u) bad |= fnd && !ok;
+                       if ((((uintptr_t)out + at) & 15u) || at > out_bytes || out_bytes - at < c.size) {
+                         if (lane == u) over = true;
+                         continue;
+                       }
+                       write_value(V, ru, ok, c, out + at, lane);
+                     }
+                     if (__ballot(over) && lane == 0u) fail(status, CRDT_ECAPACITY);
+                   });
+}
+
+// Query j's inner map -> row j of `O`, a gather by the used counts: source
+// strides are I's capacities, destination strides O's. A value whose counts
+// exceed I's capacities, an absent key and an ALL query give the empty map.
+__global__ __launch_bounds__(kBlock) void map_map_get_kernel(MapSrc S, crdt_map_mvreg_slab I, crdt_read_queries Q,
+                                                             crdt_map_mvreg_slab O, uint32_t* present, uint64_t n_obj,
+                                                             uint64_t chunks, int* status) {
+  const uint32_t A = S.A;
+  for_each_located(S, Q, n_obj, chunks, status,
+                   [&](uint64_t j, bool has, uint64_t row, bool found, uint32_t lane, bool& bad) {
+    uint32_t pres = 0u;
+    uint64_t pend = __ballot(has);
+    while (pend) {
+      const uint32_t u = (uint32_t)__builtin_ctzll(pend);
+      pend &= pend - 1u;
+      const uint64_t jr = lane64(j, u), rr = lane64(row, u);
+      bool ok = lane32(found ? 1u : 0u, u) != 0u;
+      uint32_t nk = 0u, nd = 0u;
+      if (ok) {
+        nk = I.n_keys[rr];
+        nd = I.n_def[rr];
+        bool big = nk > I.kcap || nd > I.dcap;
+        if (!big) {
+          for (uint32_t k = lane; k < nk; k += kW) big |= I.mv_n[rr * I.kcap + k] > I.mcap;
+          for (uint32_t d = lane; d < nd; d += kW) big |= I.dset_n[rr * I.dcap + d] > I.scap;
+        }
+        ok = !__ballot(big);
+        if (lane == u) {
+          pres = ok ? 1u : 0u;
+          bad |= !ok;
+        }
+        if (!ok) nk = nd = 0u;
+      }
+      for (uint32_t k = lane; k < A; k += kW) O.clock[jr * A + k] = ok ? I.clock[rr * A + k] : 0ull;
+      if (lane == 0u) {
+        O.n_keys[jr] = nk;
+        O.n_def[jr] = nd;
+      }
+      // the entries: keys, entry clocks (nk rows of A, contiguous on both sides), registers
+      for (uint32_t k = lane; k < nk; k += kW) O.keys[jr * O.kcap + k] = I.keys[rr * I.kcap + k];
+      {
+        const uint64_t* s = I.eclock + rr * I.kcap * A;
+        uint64_t* d = O.eclock + jr * O.kcap * A;
+        for (uint32_t k = lane; k < nk * A; k += kW) d[k] = s[k];
+      }
+      for (uint32_t k0 = 0; k0 < nk; k0 += kW) {
+        const uint32_t k = k0 + lane;
+        const uint32_t n = k < nk ? I.mv_n[rr * I.kcap + k] : 0u;
+        if (k < nk) O.mv_n[jr * O.kcap + k] = n;
+        const uint32_t cnt = nk - k0 < kW ? nk - k0 : kW;
+        for (uint32_t t = 0; t < cnt; ++t) {
+          const uint32_t nt = lane32(n, t);
+          const uint64_t sr = rr * I.kcap + k0 + t, dr = jr * O.kcap + k0 + t;
+          const uint64_t* sc = I.mv_clock + sr * I.mcap * A;
+          uint64_t* dc = O.mv_clock + dr * O.mcap * A;
+          for (uint32_t x = lane; x < nt * A; x += kW) dc[x] = sc[x];
+          for (uint32_t x = lane; x < nt; x += kW) O.mv_val[dr * O.mcap + x] = I.mv_val[sr * I.mcap + x];
+        }
+      }
+      // the deferred removes
+      {
+        const uint64_t* s = I.dclock + rr * I.dcap * A;
+        uint64_t* d = O.dclock + jr * O.dcap * A;
+        for (uint32_t k = lane; k < nd * A; k += kW) d[k] = s[k];
+      }
+      for (uint32_t d0 = 0; d0 < nd; d0 += kW) {
+        const uint32_t d = d0 + lane;
+        const uint32_t n = d < nd ? I.dset_n[rr * I.dcap + d] : 0u;
+        if (d < nd) O.dset_n[jr * O.dcap + d] = n;
+        const uint32_t cnt = nd - d0 < kW ? nd - d0 : kW;
+        for (uint32_t t = 0; t < cnt; ++t) {
+          const uint32_t nt = lane32(n, t);
+          const uint64_t* ss = I.dset + (rr * I.dcap + d0 + t) * I.scap;
+          uint64_t* ds = O.dset + (jr * O.dcap + d0 + t) * O.scap;
+          for (uint32_t x = lane; x < nt; x += kW) ds[x] = ss[x];
+        }
+      }
+    }
+    if (has && present) present[j] = pres;
+  });
+}
+
 template <class Src>
 int launch_read(const Src& S, const crdt_read_queries& Q, const crdt_read_sizes* Z, const crdt_read_out* O,
                 uint64_t n_obj, int* status, hipStream_t stream) {
@@ -623,6 +959,34 @@ int launch_map_mvreg_get(const crdt_map_mvreg_slab& M, const crdt_read_queries& 
   const uint64_t chunks = (n_obj + kW - 1) / kW;
   hipLaunchKernelGGL(mvreg_get_kernel, dim3(chunk_blocks(chunks)), dim3(kBlock), 0, stream, S, M.mv_n, M.mv_clock,
                      M.mv_val, M.mcap, Q, out_n, out_clk, out_val, out_cap, n_obj, chunks, status);
+  return hipGetLastError() == hipSuccess ? CRDT_OK : CRDT_EHIP;
+}
+
+int launch_map_orswot_get(const crdt_map_orswot_slab& M, const crdt_read_queries& Q, uint64_t n_obj, uint32_t A,
+                          uint64_t* sizes, uint32_t* present, uint8_t* out, const uint64_t* ooff, uint64_t out_bytes,
+                          int* status, hipStream_t stream) {
+  if (n_obj == 0) return CRDT_OK;
+  const MapSrc S{M.clock, M.n_keys, M.keys, M.eclock, M.kcap, A};
+  const OrswotVals V{M.vclock, M.vn_mem, M.vmem, M.vmclock, M.vn_def, M.vdclock, M.vdset_n, M.vdset,
+                     M.mcap,   M.vdcap,  M.vscap, A};
+  const uint64_t chunks = (n_obj + kW - 1) / kW;
+  const dim3 grid(chunk_blocks(chunks)), block(kBlock);
+  if (sizes)
+    hipLaunchKernelGGL(map_orswot_get_sizes_kernel, grid, block, 0, stream, S, V, Q, sizes, present, n_obj, chunks,
+                       status);
+  else
+    hipLaunchKernelGGL(map_orswot_get_kernel, grid, block, 0, stream, S, V, Q, out, ooff, out_bytes, n_obj, chunks,
+                       status);
+  return hipGetLastError() == hipSuccess ? CRDT_OK : CRDT_EHIP;
+}
+
+int launch_map_map_get(const crdt_map_map_slab& M, const crdt_read_queries& Q, uint64_t n_obj, uint32_t A,
+                       const crdt_map_mvreg_slab& out, uint32_t* present, int* status, hipStream_t stream) {
+  if (n_obj == 0) return CRDT_OK;
+  const MapSrc S{M.clock, M.n_keys, M.keys, M.eclock, M.kcap, A};
+  const uint64_t chunks = (n_obj + kW - 1) / kW;
+  hipLaunchKernelGGL(map_map_get_kernel, dim3(chunk_blocks(chunks)), dim3(kBlock), 0, stream, S, M.inner, Q, out,
+                     present, n_obj, chunks, status);
   return hipGetLastError() == hipSuccess ? CRDT_OK : CRDT_EHIP;
 }
 
