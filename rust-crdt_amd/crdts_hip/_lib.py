@@ -118,80 +118,104 @@ def hip_runtime():
     return C.CDLL("libamdhip64.so")
 
 
-class Ops(C.Structure):
-    """crdt_orswot_ops (include/crdts_hip.h)."""
-    _fields_ = [("obj_end", C.c_void_p), ("kind", C.c_void_p), ("member", C.c_void_p), ("actor", C.c_void_p),
-                ("counter", C.c_void_p), ("clk_end", C.c_void_p), ("clk_act", C.c_void_p),
-                ("clk_ctr", C.c_void_p), ("n_ops", C.c_size_t), ("n_clk", C.c_size_t)]
+def _spec(words):
+    """"kind:u32 key" -> (("kind", True), ("key", False)): array members in ABI
+    order, u64 elements unless marked u32."""
+    return tuple((w.split(":")[0], w.endswith(":u32")) for w in words.split())
 
 
-class MapOpsC(C.Structure):
-    """crdt_map_mvreg_ops (include/crdts_hip.h)."""
-    _fields_ = [(f, C.c_void_p) for f in ("obj_end", "kind", "key", "actor", "counter", "val", "clk_end", "clk_act",
-                                          "clk_ctr")] + [("n_ops", C.c_size_t), ("n_clk", C.c_size_t)]
+def _cstruct(pyname, cname, members):
+    return type(pyname, (C.Structure,), {"__doc__": f"{cname} (include/crdts_hip.h).", "_fields_": members})
 
 
-class MVRegOpsC(C.Structure):
-    """crdt_mvreg_ops (include/crdts_hip.h)."""
-    _fields_ = [(f, C.c_void_p) for f in ("obj_end", "val", "clk_end", "clk_act", "clk_ctr")] + \
-               [("n_ops", C.c_size_t), ("n_clk", C.c_size_t)]
+class OpLayout:
+    """One op / query struct of the ABI: its array members in ABI order with
+    their element type, then `counts`, the trailing size_t members, each with
+    the array whose length it is. `op_type` is the struct's CRDT_OPS_* code on
+    the wire (None: not an op stream of crdt_ops_*_bincode) and `wire`, for
+    an op stream, its arrays after obj_end under their crdt_op_arrays names
+    (None otherwise); `batch` is the Python class that carries it. The ctypes struct, the batch classes and ops_bincode all
+    read this one description."""
+
+    def __init__(self, pyname, cname, words, counts, op_type=None, batch=None, wire=()):
+        spec = _spec(words)
+        self.cname, self.counts, self.op_type, self.batch = cname, tuple(counts), op_type, batch
+        self.fields = tuple(f for f, _ in spec)
+        self.u32 = tuple(f for f, u in spec if u)
+        self.wire = None if op_type is None else tuple(dict(wire).get(f, f) for f in self.fields[1:])
+        self.ctype = _cstruct(pyname, cname, [(f, C.c_void_p) for f in self.fields] +
+                              [(c, C.c_size_t) for c, _ in self.counts])
 
 
-MAP_MAP_OPS_FIELDS = ("obj_end", "kind", "key", "actor", "counter", "key2", "actor2", "counter2", "val", "clk_end",
-                      "clk_act", "clk_ctr")
+_OPS_CLK = (("n_ops", "kind"), ("n_clk", "clk_act"))
+OP_LAYOUTS = {l.cname: l for l in (
+    OpLayout("Ops", "crdt_orswot_ops", "obj_end kind:u32 member actor:u32 counter clk_end clk_act:u32 clk_ctr",
+             _OPS_CLK, 0, "OrswotOps", wire={"member": "key2"}),
+    OpLayout("MVRegOpsC", "crdt_mvreg_ops", "obj_end val clk_end clk_act:u32 clk_ctr",
+             (("n_ops", "val"), ("n_clk", "clk_act")), 1, "MVRegOps"),
+    OpLayout("MapOpsC", "crdt_map_mvreg_ops",
+             "obj_end kind:u32 key actor:u32 counter val clk_end clk_act:u32 clk_ctr", _OPS_CLK, 2, "MapOps"),
+    OpLayout("MapOrswotOpsC", "crdt_map_orswot_ops",
+             "obj_end kind:u32 key actor:u32 counter member clk_end clk_act:u32 clk_ctr", _OPS_CLK, 3, "MapOrswotOps",
+             wire={"member": "key2"}),
+    OpLayout("MapMapOpsC", "crdt_map_map_ops",
+             "obj_end kind:u32 key actor:u32 counter key2 actor2:u32 counter2 val clk_end clk_act:u32 clk_ctr",
+             _OPS_CLK, 4, "MapMapOps"),
+    OpLayout("ClockOpsC", "crdt_clock_ops", "obj_end actor:u32 counter dir:u32", (("n_ops", "actor"),)),
+    OpLayout("LWWOpsC", "crdt_lwwreg_ops", "obj_end val marker", (("n_ops", "val"),)),
+    OpLayout("ReadQueriesC", "crdt_read_queries", "obj_end kind:u32 key actor:u32", (("n_q", "kind"),)),
+    OpLayout("OpArraysC", "crdt_op_arrays",
+             "kind:u32 key actor:u32 counter key2 actor2:u32 counter2 val clk_end clk_act:u32 clk_ctr", _OPS_CLK),
+)}
+Ops = OP_LAYOUTS["crdt_orswot_ops"].ctype
+MVRegOpsC = OP_LAYOUTS["crdt_mvreg_ops"].ctype
+MapOpsC = OP_LAYOUTS["crdt_map_mvreg_ops"].ctype
+MapOrswotOpsC = OP_LAYOUTS["crdt_map_orswot_ops"].ctype
+MapMapOpsC = OP_LAYOUTS["crdt_map_map_ops"].ctype
+ClockOpsC = OP_LAYOUTS["crdt_clock_ops"].ctype
+LWWOpsC = OP_LAYOUTS["crdt_lwwreg_ops"].ctype
+ReadQueriesC = OP_LAYOUTS["crdt_read_queries"].ctype
+OpArraysC = OP_LAYOUTS["crdt_op_arrays"].ctype
+OP_ARRAYS_FIELDS = OP_LAYOUTS["crdt_op_arrays"].fields
 
 
-class MapMapOpsC(C.Structure):
-    """crdt_map_map_ops (include/crdts_hip.h)."""
-    _fields_ = [(f, C.c_void_p) for f in MAP_MAP_OPS_FIELDS] + [("n_ops", C.c_size_t), ("n_clk", C.c_size_t)]
+class SlabLayout:
+    """One Map slab struct of the ABI: per array member, in ABI order, its
+    element type and its axes after the object axis — each a capacity with the
+    count array that bounds it ("kcap<n_keys": slot k of object i is used iff
+    k < n_keys[i], and so down the nesting), or "A", the actor axis, which is
+    always used — then the u32 capacities `caps`, then `inner`, the layout of
+    a nested slab struct. The ctypes struct and the slab classes (shapes,
+    dtypes, used-slot masks) read this one description."""
+
+    def __init__(self, pyname, cname, caps, members, inner=None):
+        spec = [(_spec(m.split()[0])[0], m.split()[1:]) for m in members]
+        self.cname, self.caps, self.inner = cname, tuple(caps), inner
+        self.fields = tuple(f for (f, _), _ in spec)
+        self.u32 = tuple(f for (f, u), _ in spec if u)
+        self.axes = {f: tuple(tuple(x.split("<")) if "<" in x else (x, None) for x in ax) for (f, _), ax in spec}
+        self.ctype = _cstruct(pyname, cname, [(f, C.c_void_p) for f in self.fields] +
+                              [(c, C.c_uint32) for c in self.caps] + ([("inner", inner.ctype)] if inner else []))
 
 
-class MapOrswotOpsC(C.Structure):
-    """crdt_map_orswot_ops (include/crdts_hip.h)."""
-    _fields_ = [(f, C.c_void_p) for f in ("obj_end", "kind", "key", "actor", "counter", "member", "clk_end",
-                                          "clk_act", "clk_ctr")] + [("n_ops", C.c_size_t), ("n_clk", C.c_size_t)]
-
-
-class MapSlabC(C.Structure):
-    """crdt_map_mvreg_slab (include/crdts_hip.h)."""
-    _fields_ = [(f, C.c_void_p) for f in ("clock", "n_keys", "keys", "eclock", "mv_n", "mv_clock", "mv_val", "n_def",
-                                          "dclock", "dset_n", "dset")] + \
-               [(f, C.c_uint32) for f in ("kcap", "mcap", "dcap", "scap")]
-
-
-MAP_MAP_FIELDS = ("clock", "n_keys", "keys", "eclock", "n_def", "dclock", "dset_n", "dset")
-
-
-class MapMapSlabC(C.Structure):
-    """crdt_map_map_slab (include/crdts_hip.h): the outer map and its inner Map<u64, MVReg> slab."""
-    _fields_ = [(f, C.c_void_p) for f in MAP_MAP_FIELDS] + [(f, C.c_uint32) for f in ("kcap", "dcap", "scap")] + \
-               [("inner", MapSlabC)]
-
-
-MAP_ORSWOT_FIELDS = ("clock", "n_keys", "keys", "eclock", "vclock", "vn_mem", "vmem", "vmclock", "vn_def", "vdclock",
-                     "vdset_n", "vdset", "n_def", "dclock", "dset_n", "dset")
-MAP_ORSWOT_CAPS = ("kcap", "mcap", "vdcap", "vscap", "dcap", "scap")
-
-
-class MapOrswotSlabC(C.Structure):
-    """crdt_map_orswot_slab (include/crdts_hip.h)."""
-    _fields_ = [(f, C.c_void_p) for f in MAP_ORSWOT_FIELDS] + [(f, C.c_uint32) for f in MAP_ORSWOT_CAPS]
+_MAP_OUTER = ("clock A", "n_keys:u32", "keys kcap<n_keys", "eclock kcap<n_keys A")
+_MAP_DEFERRED = ("n_def:u32", "dclock dcap<n_def A", "dset_n:u32 dcap<n_def", "dset dcap<n_def scap<dset_n")
+MAP_MVREG_SLAB = SlabLayout("MapSlabC", "crdt_map_mvreg_slab", ("kcap", "mcap", "dcap", "scap"), _MAP_OUTER + (
+    "mv_n:u32 kcap<n_keys", "mv_clock kcap<n_keys mcap<mv_n A", "mv_val kcap<n_keys mcap<mv_n") + _MAP_DEFERRED)
+MAP_MAP_SLAB = SlabLayout("MapMapSlabC", "crdt_map_map_slab", ("kcap", "dcap", "scap"), _MAP_OUTER + _MAP_DEFERRED,
+                          inner=MAP_MVREG_SLAB)  # the nested maps: key slot k of object i is inner object i * kcap + k
+MAP_ORSWOT_SLAB = SlabLayout("MapOrswotSlabC", "crdt_map_orswot_slab",
+                             ("kcap", "mcap", "vdcap", "vscap", "dcap", "scap"), _MAP_OUTER + (
+    "vclock kcap<n_keys A", "vn_mem:u32 kcap<n_keys", "vmem kcap<n_keys mcap<vn_mem",
+    "vmclock kcap<n_keys mcap<vn_mem A", "vn_def:u32 kcap<n_keys", "vdclock kcap<n_keys vdcap<vn_def A",
+    "vdset_n:u32 kcap<n_keys vdcap<vn_def", "vdset kcap<n_keys vdcap<vn_def vscap<vdset_n") + _MAP_DEFERRED)
+MapSlabC, MapMapSlabC, MapOrswotSlabC = MAP_MVREG_SLAB.ctype, MAP_MAP_SLAB.ctype, MAP_ORSWOT_SLAB.ctype
 
 
 class ClockCsr(C.Structure):
     """crdt_clock_csr (include/crdts_hip.h)."""
     _fields_ = [("off", C.c_void_p), ("len", C.c_void_p), ("act", C.c_void_p), ("ctr", C.c_void_p),
                 ("n_obj", C.c_size_t), ("n_entries", C.c_size_t)]
-
-
-class ClockOpsC(C.Structure):
-    """crdt_clock_ops (include/crdts_hip.h)."""
-    _fields_ = [(f, C.c_void_p) for f in ("obj_end", "actor", "counter", "dir")] + [("n_ops", C.c_size_t)]
-
-
-class LWWOpsC(C.Structure):
-    """crdt_lwwreg_ops (include/crdts_hip.h)."""
-    _fields_ = [(f, C.c_void_p) for f in ("obj_end", "val", "marker")] + [("n_ops", C.c_size_t)]
 
 
 class LWWViewC(C.Structure):
@@ -202,11 +226,6 @@ class LWWViewC(C.Structure):
 class MVRegViewC(C.Structure):
     """crdt_mvreg_view (include/crdts_hip.h)."""
     _fields_ = [("n", C.c_void_p), ("clk", C.c_void_p), ("val", C.c_void_p), ("cap", C.c_uint32)]
-
-
-class ReadQueriesC(C.Structure):
-    """crdt_read_queries (include/crdts_hip.h)."""
-    _fields_ = [(f, C.c_void_p) for f in ("obj_end", "kind", "key", "actor")] + [("n_q", C.c_size_t)]
 
 
 READ_SIZES_FIELDS = ("val", "slot", "dot_ctr", "add_len", "rm_len", "list_len")
@@ -238,15 +257,6 @@ class ClockCsrOut(C.Structure):
 class OpWidthsC(C.Structure):
     """crdt_op_widths (include/crdts_hip.h)."""
     _fields_ = [(f, C.c_uint32) for f in ("actor_bytes", "key_bytes", "key2_bytes", "val_bytes")]
-
-
-OP_ARRAYS_FIELDS = ("kind", "key", "actor", "counter", "key2", "actor2", "counter2", "val", "clk_end", "clk_act",
-                    "clk_ctr")
-
-
-class OpArraysC(C.Structure):
-    """crdt_op_arrays (include/crdts_hip.h)."""
-    _fields_ = [(f, C.c_void_p) for f in OP_ARRAYS_FIELDS] + [("n_ops", C.c_size_t), ("n_clk", C.c_size_t)]
 
 
 class Xfer(C.Structure):

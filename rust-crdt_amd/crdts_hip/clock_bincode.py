@@ -12,16 +12,12 @@ from __future__ import annotations
 
 import ctypes as C
 
-from ._lib import ClockCsrOut, CrdtError, check, lib
+from ._lib import CrdtError, check, lib
+from ._util import _torch, on_stream, ptr as _p
+from .batches import ClockBatch
 
 KINDS = {"vclock": 1, "gcounter": 1, "pncounter": 2}
 WIDTHS = (1, 2, 4, 8)
-
-
-def _torch():
-    import torch
-
-    return torch
 
 
 def n_clocks(kind):
@@ -65,10 +61,6 @@ def ops_extent(n_ops, stride, size):
     return (n_ops - 1) * stride + size if n_ops else 0
 
 
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
-
-
 def _csr_in(B):
     return None if B is None else B.cstruct()
 
@@ -90,32 +82,21 @@ class ClockBincodeEngine:
             out = torch.empty((n, nc * n_actors), dtype=torch.int64, device=blobs.device)
         elif out.numel() != n * nc * n_actors:
             raise CrdtError(-1, "dense rows shape mismatch")
-        check(lib.crdt_clock_dense_from_bincode(self.ctx, _p(blobs), int(blobs.numel()), _p(blob_off), _p(blob_len), n,
-                                                _width(actor_bytes), n_actors, nc, _p(out), self._stream(stream)),
-              "clock_from_bincode")
-        if check_status:
-            self.status(stream)
+        self._done(lib.crdt_clock_dense_from_bincode(self.ctx, _p(blobs), int(blobs.numel()), _p(blob_off),
+                                                     _p(blob_len), n, _width(actor_bytes), n_actors, nc, _p(out),
+                                                     self._stream(stream)),
+                   "clock_from_bincode", stream, check_status)
         return out
 
     def clock_to_bincode(self, rows, n_actors, actor_bytes, kind="vclock", stream=None, check_status=True):
         """Dense rows -> (blobs uint8, blob_off int64, blob_len int64), packed
         back to back (sizes, exclusive scan, write). A nonzero slot whose actor
         id does not fit actor_bytes latches CRDT_ENONCANON (size 0)."""
-        torch = _torch()
         nc, ab = n_clocks(kind), _width(actor_bytes)
         if rows.numel() % (nc * n_actors):
             raise CrdtError(-1, "dense rows shape mismatch")
         n = rows.numel() // (nc * n_actors)
-        st = self._stream(stream)
-        lens = torch.empty(n, dtype=torch.int64, device=rows.device)
-        check(lib.crdt_clock_dense_bincode_sizes(self.ctx, _p(rows), n, n_actors, nc, ab, _p(lens), st),
-              "clock_bincode_sizes")
-        out, off = self._placed(lens, stream)
-        check(lib.crdt_clock_dense_to_bincode(self.ctx, _p(rows), n, n_actors, nc, ab, _p(out), _p(off),
-                                              int(out.numel()), st), "clock_to_bincode")
-        if check_status:
-            self.status(stream)
-        return out, off, lens
+        return self._egest("clock_dense", (_p(rows), n, n_actors, nc, ab), n, rows.device, stream, check_status)
 
     # -------------------------------------------------------------- CSR runs
     def clock_csr_from_bincode(self, blobs, blob_off, blob_len, actor_bytes, kind="vclock", gap=0, stream=None,
@@ -123,8 +104,6 @@ class ClockBincodeEngine:
         """`to_binary` blobs -> ClockBatch (a (P, N) pair for pncounter): entry
         counts from the framing, an exclusive scan (with `gap` unused entries
         after each run), then the runs. A bad blob has len 0."""
-        from . import ClockBatch, _nullctx
-
         torch = _torch()
         nc, ab, n = n_clocks(kind), _width(actor_bytes), int(blob_off.numel())
         if blob_len.numel() != n:
@@ -135,37 +114,26 @@ class ClockBincodeEngine:
         check(lib.crdt_clock_csr_bincode_lens(*args, _p(lens[0]), _p(lens[1]) if nc == 2 else None, st),
               "clock_csr_bincode_lens")
         outs = []
-        with torch.cuda.stream(stream) if stream is not None else _nullctx():
+        with on_stream(stream):
             for ln in lens:
                 off, total = place(ln, gap)
                 cap = max(1, total)
                 outs.append(ClockBatch(off, ln, torch.empty(cap, dtype=torch.int32, device=dev),
                                        torch.empty(cap, dtype=torch.int64, device=dev), n_entries=cap))
-        w = [ClockCsrOut(_p(B.off), _p(B.len), _p(B.act), _p(B.ctr), B.n_entries) for B in outs]
-        check(lib.crdt_clock_csr_from_bincode(*args, C.byref(w[0]), C.byref(w[1]) if nc == 2 else None, st),
-              "clock_csr_from_bincode")
-        if check_status:
-            self.status(stream)
+        w = [B.cout() for B in outs]
+        self._done(lib.crdt_clock_csr_from_bincode(*args, C.byref(w[0]), C.byref(w[1]) if nc == 2 else None, st),
+                   "clock_csr_from_bincode", stream, check_status)
         return outs[0] if nc == 1 else tuple(outs)
 
     def clock_csr_to_bincode(self, S, actor_bytes, stream=None, check_status=True):
         """ClockBatch (or a (P, N) pair: PNCounter) -> (blobs uint8, blob_off
         int64, blob_len int64), packed back to back."""
-        torch = _torch()
         P, N = S if isinstance(S, (tuple, list)) else (S, None)
         if N is not None and N.n_obj != P.n_obj:
             raise CrdtError(-1, "P and N batches differ in n_obj")
-        ab, st = _width(actor_bytes), self._stream(stream)
         p, n = _csr_in(P), _csr_in(N)
-        pn = None if n is None else C.byref(n)
-        lens = torch.empty(P.n_obj, dtype=torch.int64, device=P.off.device)
-        check(lib.crdt_clock_csr_bincode_sizes(self.ctx, C.byref(p), pn, ab, _p(lens), st), "clock_csr_bincode_sizes")
-        out, off = self._placed(lens, stream)
-        check(lib.crdt_clock_csr_to_bincode(self.ctx, C.byref(p), pn, ab, _p(out), _p(off), int(out.numel()), st),
-              "clock_csr_to_bincode")
-        if check_status:
-            self.status(stream)
-        return out, off, lens
+        lead = (C.byref(p), None if n is None else C.byref(n), _width(actor_bytes))
+        return self._egest("clock_csr", lead, P.n_obj, P.off.device, stream, check_status)
 
     # ------------------------------------------------------------------- ops
     def clock_ops_from_bincode(self, blobs, n_ops, actor_bytes, with_dir=False, stride=None, stream=None,
@@ -182,11 +150,10 @@ class ClockBincodeEngine:
         actor = torch.empty(n_ops, dtype=torch.int32, device=dev)
         counter = torch.empty(n_ops, dtype=torch.int64, device=dev)
         dir_ = torch.empty(n_ops, dtype=torch.int32, device=dev) if with_dir else None
-        check(lib.crdt_clock_ops_from_bincode(self.ctx, _p(blobs), stride, n_ops, actor_bytes, int(bool(with_dir)),
-                                              _p(actor), _p(counter), _p(dir_), self._stream(stream)),
-              "clock_ops_from_bincode")
-        if check_status:
-            self.status(stream)
+        self._done(lib.crdt_clock_ops_from_bincode(self.ctx, _p(blobs), stride, n_ops, actor_bytes,
+                                                   int(bool(with_dir)), _p(actor), _p(counter), _p(dir_),
+                                                   self._stream(stream)),
+                   "clock_ops_from_bincode", stream, check_status)
         return actor, counter, dir_
 
     def clock_ops_to_bincode(self, actor, counter, dir_, actor_bytes, stride=None, out=None, stream=None,
@@ -204,9 +171,7 @@ class ClockBincodeEngine:
             out = torch.zeros(need, dtype=torch.uint8, device=actor.device)
         elif out.numel() < need:
             raise CrdtError(-4, "blob buffer too small")
-        check(lib.crdt_clock_ops_to_bincode(self.ctx, _p(actor), _p(counter), _p(dir_), n_ops, actor_bytes,
-                                            int(with_dir), _p(out), stride, self._stream(stream)),
-              "clock_ops_to_bincode")
-        if check_status:
-            self.status(stream)
+        self._done(lib.crdt_clock_ops_to_bincode(self.ctx, _p(actor), _p(counter), _p(dir_), n_ops, actor_bytes,
+                                                 int(with_dir), _p(out), stride, self._stream(stream)),
+                   "clock_ops_to_bincode", stream, check_status)
         return out

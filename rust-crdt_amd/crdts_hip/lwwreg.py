@@ -12,17 +12,12 @@ import ctypes as C
 import numpy as np
 
 from ._lib import CrdtError, LWWOpsC, LWWViewC, check, lib
+from ._util import _torch, ptr as _p
 
 # crdt_lwwreg_apply: lists of at least this many ops take the wave-per-register
 # form, shorter ones the lane-per-register loop (CRDT_LWWREG_WAVE_MIN_OPS)
 LWWREG_WAVE_MIN_OPS = 16
 LWWREG_MAX_REPS = 32  # CRDT_LWWREG_MAX_REPS
-
-def _torch():
-    import torch
-
-    return torch
-
 
 class ConflictingMarker(Exception):
     """Error::ConflictingMarker: an equal marker with a different value."""
@@ -160,10 +155,6 @@ class LWWOps:
         return LWWOpsC(*p, self.n_ops)
 
 
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
-
-
 def blob_bytes(val_bytes, marker_bytes):
     return int(val_bytes) + sum(int(b) for b in _words(marker_bytes))
 
@@ -205,10 +196,9 @@ class LWWEngine:
             n_err = torch.empty(S.n, dtype=torch.int32, device=dev)
         op_err = torch.zeros(ops.n_ops, dtype=torch.uint8, device=dev) if want_op_err else None
         c = ops.cops()
-        check(lib.crdt_lwwreg_apply(self.ctx, _p(S.val), _p(S.marker), C.byref(c), S.n, S.marker_words, _p(n_err),
-                                    _p(op_err), self._stream(stream)), "lwwreg_apply")
-        if check_status:
-            self.status(stream)
+        self._done(lib.crdt_lwwreg_apply(self.ctx, _p(S.val), _p(S.marker), C.byref(c), S.n, S.marker_words,
+                                         _p(n_err), _p(op_err), self._stream(stream)),
+                   "lwwreg_apply", stream, check_status)
         return (n_err, op_err) if want_op_err else n_err
 
     def lwwreg_fold(self, reps, out: LWWBatch | None = None, want_n_err=True, n_err=None, stream=None):
@@ -263,8 +253,7 @@ class LWWEngine:
             out = torch.zeros(need, dtype=torch.uint8, device=S.val.device)
         elif out.numel() < need:
             raise CrdtError(-4, "blob buffer too small")
-        check(lib.crdt_lwwreg_to_bincode(self.ctx, _p(S.val), _p(S.marker), S.n, val_bytes, len(mb), mb[0], mb[-1],
-                                         _p(out), stride, self._stream(stream)), "lwwreg_to_bincode")
-        if check_status:
-            self.status(stream)
+        self._done(lib.crdt_lwwreg_to_bincode(self.ctx, _p(S.val), _p(S.marker), S.n, val_bytes, len(mb), mb[0],
+                                              mb[-1], _p(out), stride, self._stream(stream)),
+                   "lwwreg_to_bincode", stream, check_status)
         return out

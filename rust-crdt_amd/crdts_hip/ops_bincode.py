@@ -15,7 +15,8 @@ from __future__ import annotations
 
 import ctypes as C
 
-from ._lib import CRDT_EINVAL, CRDT_ENONCANON, OP_ARRAYS_FIELDS, CrdtError, OpArraysC, OpWidthsC, check, lib
+from ._lib import CRDT_EINVAL, CRDT_ENONCANON, OP_ARRAYS_FIELDS, OP_LAYOUTS, CrdtError, OpArraysC, OpWidthsC, check, lib
+from ._util import _torch, on_stream, ptr as _p
 
 ORSWOT, MVREG, MAP_MVREG, MAP_ORSWOT, MAP_MAP = range(5)  # CRDT_OPS_*
 KIND_BAD = 0xFFFFFFFF  # CRDT_OP_KIND_BAD
@@ -29,22 +30,9 @@ USED_FIELDS = {
     MAP_ORSWOT: ("kind", "key", "actor", "counter", "key2"),
     MAP_MAP: ("kind", "key", "actor", "counter", "key2", "actor2", "counter2", "val"),
 }
-U32_FIELDS = ("kind", "actor", "actor2", "clk_act")
-# the batch classes' tensors after obj_end, named as in crdt_op_arrays
-LAYOUT = {
-    "OrswotOps": (ORSWOT, ("kind", "key2", "actor", "counter", "clk_end", "clk_act", "clk_ctr")),
-    "MVRegOps": (MVREG, ("val", "clk_end", "clk_act", "clk_ctr")),
-    "MapOps": (MAP_MVREG, ("kind", "key", "actor", "counter", "val", "clk_end", "clk_act", "clk_ctr")),
-    "MapOrswotOps": (MAP_ORSWOT, ("kind", "key", "actor", "counter", "key2", "clk_end", "clk_act", "clk_ctr")),
-    "MapMapOps": (MAP_MAP, ("kind", "key", "actor", "counter", "key2", "actor2", "counter2", "val", "clk_end",
-                            "clk_act", "clk_ctr")),
-}
-
-
-def _torch():
-    import torch
-
-    return torch
+U32_FIELDS = OP_LAYOUTS["crdt_op_arrays"].u32
+# per batch class: its op type, and its tensors after obj_end named as in crdt_op_arrays (views of _lib.OP_LAYOUTS)
+LAYOUT = {l.batch: (l.op_type, l.wire) for l in OP_LAYOUTS.values() if l.op_type is not None}
 
 
 def check_widths(op_type, widths):
@@ -86,10 +74,6 @@ def op_blob_bytes(op_type, kind, n_pairs, widths):
     return sizes[kind]
 
 
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
-
-
 def _cwidths(op_type, widths):
     return OpWidthsC(*check_widths(op_type, widths))
 
@@ -110,10 +94,9 @@ class OpsBincodeEngine:
             raise CrdtError(CRDT_EINVAL, "blob_off / blob_len lengths differ")
         w = _cwidths(op_type, widths)
         lens = torch.zeros(n, dtype=torch.int32, device=blobs.device)
-        check(lib.crdt_ops_bincode_clk_lens(self.ctx, _p(blobs), int(blobs.numel()), _p(blob_off), _p(blob_len), n,
-                                            op_type, C.byref(w), _p(lens), self._stream(stream)), "ops_clk_lens")
-        if check_status:
-            self.status(stream)
+        self._done(lib.crdt_ops_bincode_clk_lens(self.ctx, _p(blobs), int(blobs.numel()), _p(blob_off), _p(blob_len),
+                                                 n, op_type, C.byref(w), _p(lens), self._stream(stream)),
+                   "ops_clk_lens", stream, check_status)
         return lens
 
     def ops_from_bincode(self, blobs, blob_off, blob_len, op_type, widths, op_err=False, stream=None,
@@ -122,12 +105,10 @@ class OpsBincodeEngine:
         fields op_type uses, clk_end, clk_act, clk_ctr; `op_err`: also the
         per-op codes, int32): the framing pass, a cumsum on the device, then
         the fields and the pairs. A bad op has kind KIND_BAD and zero fields."""
-        from . import _nullctx
-
         torch = _torch()
         n, dev = int(blob_off.numel()), blobs.device
         lens = self.ops_clk_lens(blobs, blob_off, blob_len, op_type, widths, stream, check_status=False)
-        with torch.cuda.stream(stream) if stream is not None else _nullctx():
+        with on_stream(stream):
             clk_end = torch.cumsum(lens.to(torch.int64), 0)
             n_clk = int(clk_end[-1].item()) if n else 0
             a = {f: torch.empty(n, dtype=torch.int32 if f in U32_FIELDS else torch.int64, device=dev)
@@ -137,10 +118,9 @@ class OpsBincodeEngine:
             a["clk_ctr"] = torch.empty(n_clk, dtype=torch.int64, device=dev)
             err = torch.zeros(n, dtype=torch.int32, device=dev) if op_err else None
         w, c = _cwidths(op_type, widths), _carrays(a, n, n_clk)
-        check(lib.crdt_ops_from_bincode(self.ctx, _p(blobs), int(blobs.numel()), _p(blob_off), _p(blob_len), op_type,
-                                        C.byref(w), C.byref(c), _p(err), self._stream(stream)), "ops_from_bincode")
-        if check_status:
-            self.status(stream)
+        self._done(lib.crdt_ops_from_bincode(self.ctx, _p(blobs), int(blobs.numel()), _p(blob_off), _p(blob_len),
+                                             op_type, C.byref(w), C.byref(c), _p(err), self._stream(stream)),
+                   "ops_from_bincode", stream, check_status)
         if op_err:
             a["op_err"] = err
         return a
@@ -160,18 +140,17 @@ class OpsBincodeEngine:
         lens = torch.zeros(n, dtype=torch.int64, device=arrays["clk_end"].device)
         check(lib.crdt_ops_bincode_sizes(self.ctx, op_type, C.byref(w), C.byref(c), _p(lens), st), "ops_bincode_sizes")
         out, off = self._placed(lens, stream)
-        check(lib.crdt_ops_to_bincode(self.ctx, op_type, C.byref(w), C.byref(c), _p(out), _p(off), int(out.numel()),
-                                      st), "ops_to_bincode")
-        if check_status:
-            self.status(stream)
+        self._done(lib.crdt_ops_to_bincode(self.ctx, op_type, C.byref(w), C.byref(c), _p(out), _p(off),
+                                           int(out.numel()), st), "ops_to_bincode", stream, check_status)
         return out, off, lens
 
 
 def _layout(cls):
-    for k in cls.__mro__:
-        if k.__name__ in LAYOUT:
-            return LAYOUT[k.__name__]
-    raise CrdtError(CRDT_EINVAL, f"{cls.__name__} is not an op batch class")
+    """The layout of an op-stream batch class (its own or an ancestor's)."""
+    lay = getattr(cls, "LAYOUT", None)
+    if lay is None or lay.op_type is None:
+        raise CrdtError(CRDT_EINVAL, f"{cls.__name__} is not an op batch class")
+    return lay
 
 
 def ops_from_wire(cls, blobs, blob_off, blob_len, obj_end, widths, engine=None, stream=None, check_status=True):
@@ -180,22 +159,23 @@ def ops_from_wire(cls, blobs, blob_off, blob_len, obj_end, widths, engine=None, 
     wire."""
     import numpy as np
 
-    from . import default_engine
+    from .host_model import default_engine
 
     torch = _torch()
     engine = engine or default_engine()
     if not torch.is_tensor(obj_end):
         obj_end = torch.from_numpy(np.ascontiguousarray(np.asarray(obj_end, np.uint64)).view(np.int64)).to(
             blobs.device)
-    op_type, fields = _layout(cls)
-    a = engine.ops_from_bincode(blobs, blob_off, blob_len, op_type, widths, stream=stream, check_status=check_status)
-    return cls(obj_end, *[a[f] for f in fields])
+    lay = _layout(cls)
+    a = engine.ops_from_bincode(blobs, blob_off, blob_len, lay.op_type, widths, stream=stream,
+                                check_status=check_status)
+    return cls(obj_end, *[a[f] for f in lay.wire])
 
 
 def ops_to_wire(ops, widths, engine=None, stream=None, check_status=True):
     """ops.to_bincode: an op batch -> (blobs, blob_off, blob_len)."""
-    from . import default_engine
+    from .host_model import default_engine
 
-    op_type, fields = _layout(type(ops))
-    return (engine or default_engine()).ops_to_bincode(op_type, widths, dict(zip(fields, ops.t[1:])), stream,
+    lay = _layout(type(ops))
+    return (engine or default_engine()).ops_to_bincode(lay.op_type, widths, dict(zip(lay.wire, ops.t[1:])), stream,
                                                        check_status)
