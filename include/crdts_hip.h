@@ -1410,8 +1410,20 @@ int crdt_map_map_get(crdt_ctx* ctx, const crdt_map_map_slab* slab, const crdt_re
  * bytes) latches CRDT_ENONCANON; one with more than 16384 members or more
  * than 1024 deferred clocks latches CRDT_ECAPACITY, and so do the objects of
  * one call past its first 65536 with more than 256 members or 64 deferred
- * clocks (those are decoded by a second kernel from an HBM scratch).
- *   1) crdt_orswot_bincode_record_sizes: d_sizes[i] = record bytes (0 if bad)
+ * clocks (those are decoded by a second kernel from an HBM scratch). A blob's
+ * length words are read front to back before anything else of it is looked
+ * at, and the first that cannot be taken decides the code: a member or
+ * deferred-clock count above the capacity is CRDT_ECAPACITY where it is read,
+ * whatever the clocks before it hold and however few bytes follow it. 24 zero
+ * bytes are valid (Orswot::default()). The other blobs of the call are
+ * decoded as if the refused one were not there; of a refused blob nothing is
+ * written outside the slot placed for it.
+ *   1) crdt_orswot_bincode_record_sizes: d_sizes[i] = record bytes; 0 (and
+ *      the code latched) for a blob whose length words are refused or that
+ *      is not inside d_blobs. A blob that is bad only in what its fields hold
+ *      (a zero counter, an actor >= n_actors or out of order, duplicates) is
+ *      sized by its counts here and refused by crdt_orswot_from_bincode
+ *      (the slot's contents are then unspecified)
  *      — or, without reading the blobs, crdt_orswot_bincode_record_bounds:
  *      d_bounds[i] >= the record bytes of any blob of length blob_len[i]
  *      (16-B multiple; <= 48 + 8 n_actors + blob_len * max(12/(wa+8),
@@ -1424,7 +1436,10 @@ int crdt_map_map_get(crdt_ctx* ctx, const crdt_map_map_slab* slab, const crdt_re
  * state by from_binary:
  *   1) crdt_orswot_bincode_sizes: d_sizes[i] = blob bytes
  *   2) the caller places blobs at 16-B aligned offsets (each zero-padded to 16)
- *   3) crdt_orswot_to_bincode writes them.                                    */
+ *   3) crdt_orswot_to_bincode writes them; a member key or an actor id that
+ *      does not fit its byte width latches CRDT_ENONCANON (the blob's bytes
+ *      are then unspecified), and so does the whole call, whatever its
+ *      records hold, when n_actors - 1 does not fit actor_bytes.              */
 int crdt_orswot_bincode_record_sizes(crdt_ctx* ctx, const uint8_t* d_blobs, size_t blob_bytes,
                                      const uint64_t* d_blob_off, const uint64_t* d_blob_len, size_t n_obj,
                                      uint32_t actor_bytes, uint32_t member_bytes, uint32_t n_actors,

@@ -802,9 +802,41 @@ double orc_orswot_bench(const uint8_t* lb, const uint64_t* loff, size_t lbytes,
 // Blob -> canonical record (0 ok / -2 not decodable or not canonical / -4 cap).
 long orc_bincode_to_record(const uint8_t* blob, size_t n, int wa, int wm, uint32_t n_actors, uint32_t flags,
                            uint8_t* out, size_t cap) {
+  // The length words first, front to back, before any content is looked at: a
+  // count above the record's capacity (16384 members, 1024 deferred clocks)
+  // is CRDT_ECAPACITY where it is read, whatever the clocks before it hold.
+  {
+    BinReader r{blob, n};
+    auto skip_clock = [&]() {
+      const uint64_t k = r.get(8);
+      if (!r.ok || k > r.n - r.pos || k * (uint64_t)(wa + 8) > r.n - r.pos) return false;
+      r.pos += k * (wa + 8);
+      return true;
+    };
+    if (!skip_clock()) return -2;
+    const uint64_t ne = r.get(8);
+    if (!r.ok) return -2;
+    if (ne > 16384) return -4;
+    for (uint64_t i = 0; i < ne; ++i) {
+      r.get(wm);
+      if (!r.ok || !skip_clock()) return -2;
+    }
+    const uint64_t nd = r.get(8);
+    if (!r.ok) return -2;
+    if (nd > 1024) return -4;
+  }
   Orswot o;
   if (!from_binary(blob, n, wa, wm, o)) return -2;
-  for (const auto& kv : o.clock.dots) if (kv.first >= n_actors || kv.second == 0) return -2;
+  // what a record cannot hold: a zero counter or an actor >= n_actors in any
+  // clock, an empty member clock, an empty deferred clock or set
+  auto clock_ok = [&](const VClock& v, bool may_be_empty) {
+    if (v.dots.empty() && !may_be_empty) return false;
+    for (const auto& kv : v.dots) if (kv.first >= n_actors || kv.second == 0) return false;
+    return true;
+  };
+  if (!clock_ok(o.clock, true)) return -2;
+  for (const auto& e : o.entries) if (!clock_ok(e.second, false)) return -2;
+  for (const auto& d : o.deferred) if (!clock_ok(d.first, false) || d.second.empty()) return -2;
   return encode(o, n_actors, out, cap, (flags & CRDT_ORSWOT_SPARSE_CLOCK) != 0);
 }
 

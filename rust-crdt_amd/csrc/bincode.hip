@@ -340,6 +340,9 @@ __device__ __forceinline__ int bc_write_record(const SRC& B, const BcWalk& w, ui
     }
   }
   sync<XL::kGlobal>();
+  // two equal keys share a rank and leave another rank's slot of Sm as the
+  // previous object left it: no offset may be taken from it
+  if (__ballot(bad)) return CRDT_ENONCANON;
   bc_scan_excl<XL>(Sm, w.n_mem, lane);
   bc_mark<ST>(st, 3);
   for (uint32_t e = lane; e < w.n_mem; e += kBcWave) {
@@ -379,6 +382,7 @@ __device__ __forceinline__ int bc_write_record(const SRC& B, const BcWalk& w, ui
       Ss[r < XL::kDef ? r : 0u] = Ls[d];
     }
     sync<XL::kGlobal>();
+    if (__ballot(bad)) return CRDT_ENONCANON;  // (equal clocks: a slot of Sd / Ss is stale, as above)
     bc_scan_excl<XL>(Sd, w.n_def, lane);
     bc_scan_excl<XL>(Ss, w.n_def, lane);
     for (uint32_t d = lane; d < w.n_def; d += kBcWave) {

@@ -241,14 +241,22 @@ def orswot_merge_batch(lbase, loff, rbase, roff, n_actors, threads=8, flags=0):
     return obase, ooff
 
 
-def bincode_to_record(blob, wa, wm, n_actors, flags=0):
-    """Blob -> canonical record through the C++ restatement (oracle/ref_cpu.cpp)."""
+def bincode_to_record(blob, wa, wm, n_actors, flags=0, cap=1 << 16):
+    """Blob -> canonical record (of at most cap bytes) through the C++ restatement (oracle/ref_cpu.cpp)."""
     b = np.frombuffer(bytes(blob) or b"\0", dtype=np.uint8)
-    out = np.zeros(1 << 16, dtype=np.uint8)
+    out = np.zeros(cap, dtype=np.uint8)
     n = lib().orc_bincode_to_record(_ptr(b), len(blob), wa, wm, n_actors, flags, _ptr(out), out.nbytes)
     if n < 0:
         raise ValueError(f"oracle bincode decode failed rc={n}")
     return out[:n].tobytes()
+
+
+def bincode_verdict(blob, wa, wm, n_actors, flags=0, cap=1 << 16):
+    """-> (0, record) or (the oracle's CRDT_E* code, None) for one blob."""
+    b = np.frombuffer(bytes(blob) or b"\0", dtype=np.uint8)
+    out = np.zeros(cap, dtype=np.uint8)
+    n = lib().orc_bincode_to_record(_ptr(b), len(blob), wa, wm, n_actors, flags, _ptr(out), out.nbytes)
+    return (int(n), None) if n < 0 else (0, out[:n].tobytes())
 
 
 def bincode_ingest_bench(blobs, off, lens, wa, wm, n_actors, flags, threads):
