@@ -155,6 +155,75 @@ int crdt_pncounter_csr_merge(crdt_ctx* ctx, const crdt_clock_csr* self_p, const 
                              const crdt_clock_csr_out* out_p, const crdt_clock_csr_out* out_n, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * Clock and counter fold (clock_fold.hip): out[i] = reps[0][i].merge(reps[1][i])
+ * .merge(reps[2][i])... of VClock::merge (src/vclock.rs:131-137), which is
+ * GCounter::merge (src/gcounter.rs:58-62) and, on P and on N, PNCounter::merge
+ * (src/pncounter.rs:90-95), in rank order, the fixed-order convention of
+ * crdt_orswot_fold, crdt_lwwreg_fold and crdt_mvreg_fold. One launch: every
+ * replica entry is read once, the output is written once, no intermediate
+ * batch exists and the host is not synchronised. h_rows / h_reps are HOST
+ * arrays of n_reps device pointers / views.
+ *
+ * crdt_clock_dense_fold: d_out[i][a] = max over r of h_rows[r][i][a], over
+ * rows of n_slots words (n_actors for VClock and GCounter, 2 * n_actors for
+ * PNCounter's [P|N] rows, as in crdt_dense_merge_host). Flat over n_obj *
+ * n_slots words: R + 1 words of traffic per slot. d_out may be any h_rows[r]
+ * (a word is read from every replica before it is written). n_reps == 1
+ * copies through; n_reps == 2 gives crdt_vclock_dense_merge's bytes.
+ *
+ * crdt_clock_csr_fold: out[i] = the sorted union of object i's R runs with
+ * the largest counter per actor. out.off[i] := the sum over r of
+ * reps[r].off[i], out.len[i] := the union's length: the offsets, lengths and
+ * entries the chain of crdt_vclock_csr_merge ends with. out.n_entries >= the
+ * sum of the replicas' n_entries suffices (CRDT_ECAPACITY otherwise) and the
+ * output is itself a valid (gapped) input batch. Object i's region is
+ * [out.off[i], out.off[i] + the sum over r of reps[r].len[i]); regions are
+ * disjoint whenever every replica is placed correctly. The kernel may use a
+ * region as scratch: cells of it past out.len[i] are unspecified (as the
+ * merge's gaps are); nothing outside the regions, out.off and out.len is
+ * written, and no caller scratch is needed. n_reps == 1 copies the runs
+ * through, checked; n_reps == 2 equals crdt_vclock_csr_merge in off, len, used
+ * entries and codes. PNCounter is two calls, P and N. Runs of any length.
+ *
+ * CRDT_EINVAL, before any device work: null ctx, h_rows, h_reps or out; n_reps
+ * 0 or > CRDT_CLOCK_FOLD_MAX_REPS; replicas whose n_obj differ; n_slots 0; a
+ * null array with n_obj > 0 (a null act / ctr with n_entries > 0); a CSR out
+ * array equal to a replica's array. n_obj == 0 is CRDT_OK and launches nothing.
+ * Latched per object (out.len[i] = 0, every other object folded): CRDT_EINVAL
+ * for a run of any replica out of its arrays or overlapping its neighbour
+ * (off[i] + len[i] > off[i+1]) and for a region that does not fit
+ * out.n_entries; CRDT_ENONCANON for a run of any replica that is not canonical
+ * (actors not strictly increasing, a zero counter). For R > 2 this is the one
+ * difference from the chain: the chain restarts an object's union from empty
+ * after a step that met a bad run and goes on with the later replicas; the
+ * fold leaves the object empty.
+ *
+ * Tiers, per object on the device, by T = the sum of its R lengths:
+ *   T <= 64: the union is built in registers (one lane per entry);
+ *   T <= CRDT_CLOCK_FOLD_STAGE_ENTRIES: the runs are staged in LDS. A wave's
+ *     LDS is 14 B per entry (actor, counter, a u16 index) + 96 B = 7,264 B at
+ *     512 entries; a block of 4 waves 29,056 B; 5 blocks, 20 waves (5 per
+ *     SIMD), fit a CU's 160 KB (the kernel's 110 registers make it 4 per
+ *     SIMD). 512 covers 8 replicas of the ~48-entry clocks measured below;
+ *   longer: binary searches in HBM, the object's own region as scratch.
+ *
+ * Fold or chain (measured, 1M objects). Dense rows of 16
+ * slots: the fold at every R — one crdt_vclock_dense_merge's time at R = 2
+ * (0.998x, inside the merge's spread), 0.56x the chain of R - 1 merges at
+ * R = 4, 0.45x at R = 8. CSR clocks of ~48 entries: the fold from R = 3 on —
+ * 0.62x the chain at R = 4, 0.49x at R = 8, and no intermediate batches — but
+ * at R = 2 call crdt_vclock_csr_merge: two such runs sum past 64 entries, so
+ * the fold takes its LDS tier and 2.64x the time of the merge, which joins
+ * runs of up to 64 entries a side in registers.
+ * ------------------------------------------------------------------------ */
+#define CRDT_CLOCK_FOLD_MAX_REPS 32
+#define CRDT_CLOCK_FOLD_STAGE_ENTRIES 512
+int crdt_clock_dense_fold(crdt_ctx* ctx, const uint64_t* const* h_rows, uint32_t n_reps, uint64_t* d_out,
+                          size_t n_obj, uint32_t n_slots, void* stream);
+int crdt_clock_csr_fold(crdt_ctx* ctx, const crdt_clock_csr* h_reps, uint32_t n_reps,
+                        const crdt_clock_csr_out* out, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * Batched op path of the clocks and counters (clock_ops.hip): CmRDT::apply,
  * Causal::truncate, the reads, and the two primitives the reference builds
  * the rest from (subtract, intersection), on dense rows and on CSR runs.

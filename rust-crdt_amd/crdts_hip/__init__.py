@@ -17,7 +17,7 @@ import os  # noqa: F401
 
 import numpy as np  # noqa: F401
 
-from ._lib import (CRDT_COMM_ID_BYTES, CRDT_ECAPACITY, CRDT_EINVAL, CRDT_ENONCANON, CRDT_OK, EXPORTS, LIB_PATH, SPARSE_CLOCK, Batch, CrdtError,
+from ._lib import (CLOCK_FOLD_MAX_REPS, CLOCK_FOLD_STAGE_ENTRIES, CRDT_COMM_ID_BYTES, CRDT_ECAPACITY, CRDT_EINVAL, CRDT_ENONCANON, CRDT_OK, EXPORTS, LIB_PATH, SPARSE_CLOCK, Batch, CrdtError,
                    GenParams, RepParams, check, lib)
 from ._util import _nullctx, _torch
 from .batches import ClockBatch, OrswotBatch
@@ -43,5 +43,5 @@ __all__ = [
     "generate_clocks_csr", "MapMapSlab", "MapOps", "MapMapOps", "MVRegOps", "ClockOps",
     "ReadQueries", "LWWReg", "LWWBatch", "LWWOps", "ConflictingMarker", "LWWREG_WAVE_MIN_OPS", "LWWREG_MAX_REPS",
     "MapSlab", "MapOrswotSlab", "OrswotOps", "MapOrswotOps", "generate_orswot_tail", "generate_orswot_csr_tail",
-    "default_engine", "build_record",
+    "default_engine", "build_record", "CLOCK_FOLD_MAX_REPS", "CLOCK_FOLD_STAGE_ENTRIES",
 ]

@@ -98,9 +98,12 @@ EXPORTS = [
     "crdt_clock_csr_bincode_lens", "crdt_clock_csr_from_bincode", "crdt_clock_csr_bincode_sizes",
     "crdt_clock_csr_to_bincode", "crdt_clock_ops_from_bincode", "crdt_clock_ops_to_bincode",
     "crdt_ops_bincode_clk_lens", "crdt_ops_from_bincode", "crdt_ops_bincode_sizes", "crdt_ops_to_bincode",
+    "crdt_clock_dense_fold", "crdt_clock_csr_fold",
 ]
 
 CRDT_COMM_ID_BYTES = 128
+CLOCK_FOLD_MAX_REPS = 32  # CRDT_CLOCK_FOLD_MAX_REPS
+CLOCK_FOLD_STAGE_ENTRIES = 512  # CRDT_CLOCK_FOLD_STAGE_ENTRIES: the longest sum of an object's runs that is folded in LDS
 
 
 def hip_runtime():
@@ -382,6 +385,8 @@ def _load():
         "crdt_vclock_csr_merge": (I, [P, C.POINTER(ClockCsr), C.POINTER(ClockCsr), C.POINTER(ClockCsrOut), P]),
         "crdt_gcounter_csr_merge": (I, [P, C.POINTER(ClockCsr), C.POINTER(ClockCsr), C.POINTER(ClockCsrOut), P]),
         "crdt_pncounter_csr_merge": (I, [P] + [C.POINTER(ClockCsr)] * 4 + [C.POINTER(ClockCsrOut)] * 2 + [P]),
+        "crdt_clock_dense_fold": (I, [P, C.POINTER(P), U32, P, SZ, U32, P]),
+        "crdt_clock_csr_fold": (I, [P, C.POINTER(ClockCsr), U32, C.POINTER(ClockCsrOut), P]),
         "crdt_vclock_dense_apply": (I, [P, P, C.POINTER(ClockOpsC), SZ, U32, P]),
         "crdt_gcounter_apply": (I, [P, P, C.POINTER(ClockOpsC), SZ, U32, P]),
         "crdt_pncounter_apply": (I, [P, P, C.POINTER(ClockOpsC), SZ, U32, P]),

@@ -149,6 +149,50 @@ class ClockEngine:
                                                 self._stream(stream)), "pncounter_csr_merge", stream, check_status)
         return op, on
 
+    # ------------------------------------------------ the fold of R replicas
+    def dense_fold(self, rows_list, n_slots, out=None, stream=None):
+        """out = the pointwise max of 1..32 replicas' dense rows, one launch
+        (crdt_clock_dense_fold): the chain rows_list[0].merge(rows_list[1])...
+        of VClock / GCounter rows (n_slots = n_actors) or PNCounter [P|N] rows
+        (n_slots = 2 * n_actors). `out` may be one of the replicas (in place);
+        default: a new tensor."""
+        torch = _torch()
+        numel = int(rows_list[0].numel()) if rows_list else 0
+        if any(int(r.numel()) != numel for r in rows_list) or (n_slots and numel % n_slots):
+            raise CrdtError(-1, "dense rows shape mismatch")
+        if out is None and rows_list:
+            out = torch.empty_like(rows_list[0])
+        if out is not None and int(out.numel()) != numel:
+            raise CrdtError(-1, "dense rows shape mismatch")
+        ptrs = (C.c_void_p * max(1, len(rows_list)))(*[r.data_ptr() or None for r in rows_list])
+        check(lib.crdt_clock_dense_fold(self.ctx, ptrs, len(rows_list), dptr(out) if out is not None else None,
+                                        numel // n_slots if n_slots else 0, n_slots, self._stream(stream)),
+              "dense fold")
+        return out
+
+    def clock_csr_fold(self, reps, out: "ClockBatch | None" = None, stream=None, check_status=True):
+        """out[i] = reps[0][i].merge(reps[1][i]).merge(reps[2][i])... over 1..32
+        replicas' sparse clock batches, one launch (crdt_clock_csr_fold): the
+        sorted union with the largest counter per actor, placed at the sum of
+        the replicas' offsets; `out` defaults to a new batch of the summed
+        n_entries. GCounter alike; PNCounter: pncounter_csr_fold."""
+        from ._lib import ClockCsr
+
+        n_obj = reps[0].n_obj if reps else 0
+        out = out or self._csr_out(n_obj, sum(r.n_entries for r in reps))
+        views = (ClockCsr * max(1, len(reps)))(*[r.cstruct() for r in reps])
+        w = out.cout()
+        self._done(lib.crdt_clock_csr_fold(self.ctx, views, len(reps), C.byref(w), self._stream(stream)),
+                   "clock_csr_fold", stream, check_status)
+        return out
+
+    def pncounter_csr_fold(self, P_list, N_list, outs=None, stream=None, check_status=True):
+        """PNCounter::merge (src/pncounter.rs:90-95) folded over R replicas'
+        sparse P and N clocks: two folds; returns (out_p, out_n)."""
+        op, on = outs or (None, None)
+        return (self.clock_csr_fold(P_list, out=op, stream=stream, check_status=check_status),
+                self.clock_csr_fold(N_list, out=on, stream=stream, check_status=check_status))
+
     def clock_csr_truncate(self, S: "ClockBatch", O: "ClockBatch", out=None, stream=None, check_status=True):
         """out[i] = S[i] after Causal::truncate(&O[i]) (src/vclock.rs:103-120), placed at S.off."""
         return self._csr_filter(lib.crdt_vclock_csr_truncate, "csr truncate", S, O, out, stream, check_status)

@@ -372,6 +372,39 @@ int crdt_vclock_csr_get(crdt_ctx* ctx, const crdt_clock_csr* self, const crdt_cl
   return launch_clock_csr_get(*self, *queries, d_out, ctx->d_status, S(stream));
 }
 
+// ---- the clocks' fold (clock_fold.hip)
+int crdt_clock_dense_fold(crdt_ctx* ctx, const uint64_t* const* h_rows, uint32_t n_reps, uint64_t* d_out, size_t n_obj,
+                          uint32_t n_slots, void* stream) {
+  if (!ctx || !h_rows || n_reps == 0 || n_reps > CRDT_CLOCK_FOLD_MAX_REPS || n_slots == 0) return CRDT_EINVAL;
+  if (n_obj) {
+    if (!d_out) return CRDT_EINVAL;
+    for (uint32_t r = 0; r < n_reps; ++r)
+      if (!h_rows[r]) return CRDT_EINVAL;
+  }
+  if (n_obj == 0) return CRDT_OK;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_clock_dense_fold(h_rows, n_reps, d_out, (uint64_t)n_obj * n_slots, S(stream));
+}
+int crdt_clock_csr_fold(crdt_ctx* ctx, const crdt_clock_csr* h_reps, uint32_t n_reps, const crdt_clock_csr_out* out,
+                        void* stream) {
+  if (!ctx || !h_reps || n_reps == 0 || n_reps > CRDT_CLOCK_FOLD_MAX_REPS) return CRDT_EINVAL;
+  const size_t n_obj = h_reps[0].n_obj;
+  size_t total = 0;
+  for (uint32_t r = 0; r < n_reps; ++r) {
+    if (!csr_in_ok(&h_reps[r]) || h_reps[r].n_obj != n_obj) return CRDT_EINVAL;
+    total += h_reps[r].n_entries;
+  }
+  if (!csr_out_ok(out, n_obj)) return CRDT_EINVAL;
+  for (uint32_t r = 0; n_obj && r < n_reps; ++r)
+    if (csr_alias(&h_reps[r], out)) return CRDT_EINVAL;
+  if (out->n_entries < total) return CRDT_ECAPACITY;
+  if (n_obj == 0) return CRDT_OK;
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  return launch_clock_csr_fold(h_reps, n_reps, *out, ctx->d_status, S(stream));
+}
+
 int crdt_orswot_truncate(crdt_ctx* ctx, const crdt_orswot_batch* self, const crdt_clock_csr* clocks,
                          uint32_t n_actors, uint32_t flags, uint8_t* d_out, uint64_t* d_out_off, size_t out_bytes,
                          void* stream) {

@@ -28,6 +28,14 @@ int launch_orswot_merge_sparse(const uint8_t* Lb, const uint64_t* Loff, uint64_t
 int launch_clock_csr_merge(const crdt_clock_csr* const* self, const crdt_clock_csr* const* other,
                            const crdt_clock_csr_out* const* out, int n_jobs, int* status, hipStream_t stream);
 
+// Clock fold (clock_fold.hip): rows / reps are host arrays of 1 <= n_reps <=
+// CRDT_CLOCK_FOLD_MAX_REPS device pointers / views of one n_obj (api.hip checks
+// the rest); out may be one of rows; the CSR out is sized for the entries' sum.
+int launch_clock_dense_fold(const uint64_t* const* rows, uint32_t n_reps, uint64_t* out, uint64_t n_words,
+                            hipStream_t stream);
+int launch_clock_csr_fold(const crdt_clock_csr* reps, uint32_t n_reps, const crdt_clock_csr_out& out, int* status,
+                          hipStream_t stream);
+
 int launch_orswot_truncate(const crdt_orswot_batch& self, const crdt_clock_csr& clocks, uint32_t A, uint32_t flags,
                            uint8_t* out, uint64_t* out_off, uint64_t out_bytes, int* status, uint32_t* ctl,
                            uint64_t* list, uint32_t list_cap, hipStream_t stream);
